@@ -7,14 +7,22 @@ apply) and the no-blend composite (mapper.cpp:193-312).  A step = one Mapper::st
 set, inputs and outputs resident in HBM.  Multi-GPU: one process per GPU, each stitches its own
 independent rig (rigs shard with no collective) -> "scaling": "weak".
 
-Prints ONE JSON line on rank 0.  Extra objects: "roofline" (the composite kernel, HIP-event timed
-live over the timed region) and "cpu_baseline" (the oracle restatement of the reference CPU path,
-timed on this host).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line with
+"roofline" (the composite kernel, HIP-event timed live over the timed region, so it costs no run of its own).
+--full adds what takes runs of its own after the timed region: "cpu_baseline" (the oracle restatement of the
+reference CPU path, timed on this host), "async_e2e", "roofline_one_in_flight", "survey_b_alg" and, for F2, the
+"roofline" of 16 back-to-back frames.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--no-cpu-baseline] [--preroll S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--preroll S] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-async-e2e]]
 
 K timed steps (default 1,000) follow W warmup steps and S seconds (default 0.5) of untimed preroll steps,
 so that the timed region runs at the GPU's settled clock.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed call left in its output frames as
+DIR/stitched.npy (float32; a fixed, seeded sample of the bytes when the frames hold more than DUMP_SAMPLE) and
+the gains that call estimated as DIR/gains.npy (float64).  Frames are seeded, so the same arguments give the
+same inputs from run to run.
 
 Diagnostics (Mapper configs; DESIGN.md §4 Round 6, "The 20-step region"): OCTVR_BENCH_STEP_MARKS=<file> appends
 the host time at which each timed step returned, the GPU span between markers at the region's ends and every
@@ -42,7 +50,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="C2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the measurements that take runs of their own: the CPU "
+                         "baseline, the AsyncMultiMapper end to end, the one-in-flight kernel time, the survey's "
+                         "byte model (and F2's roofline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed call computed as DIR/<name>.npy (float32 / float64; a fixed, "
+                         "seeded sample of a large frame)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--inflight", type=int, default=None,
                     help="frames in flight: independent frame sets stitched round-robin on this many streams "
                          "(octvr_mapper_set_frames_in_flight); default per config, DEFAULT_INFLIGHT")
@@ -51,7 +66,7 @@ def parse():
                          "frames in flight): 8 C2 sets are 600 MB, more than the 256 MB Infinity Cache, so every "
                          "step reads its sources from HBM as a live pipeline's fresh frames would be")
     ap.add_argument("--no-async-e2e", action="store_true",
-                    help="skip the AsyncMultiMapper end-to-end (PCIe-inclusive) measurement")
+                    help="with --full: skip the AsyncMultiMapper end-to-end (PCIe-inclusive) measurement")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-gain", action="store_true", help=argparse.SUPPRESS)  # diagnostic: composite alone
     ap.add_argument("--preroll", type=float, default=0.5,
@@ -164,6 +179,39 @@ def timed_region(step, steps, sync, dist=None):
 def aggregate_mps(world, steps, frame_px, elapsed):
     """Whole-job throughput: every rank stitched `steps` frames of `frame_px` output pixels."""
     return world * steps * frame_px / 1e6 / elapsed
+
+
+DUMP_SAMPLE = 8 << 20  # values of stitched.npy at the most (32 MB of float32)
+DUMP_SEED = 20240531
+
+
+def output_sample(frames):
+    """float32 numpy array of the output frames' bytes (a list of equally shaped uint8 tensors, stacked): all
+    of them up to DUMP_SAMPLE values, else the values at DUMP_SAMPLE sorted positions drawn once from
+    DUMP_SEED (the same positions for every run of the same shape)."""
+    import numpy as np
+    import torch
+    flat = torch.stack(list(frames)).reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_SAMPLE))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(out_dir, arrays, rank=0):
+    """DIR/<name>.npy for rank 0, DIR/<name>_rank<r>.npy for the other ranks of a multi-GPU run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(out_dir, name + ("_rank%d" % rank if rank else "") + ".npy"), a)
+
+
+def last_outputs(outs, calls, inflight, nb):
+    """The output frames the last of `calls` timed calls wrote (call c writes the nb outputs of stream
+    c % inflight)."""
+    j = (calls - 1) % inflight
+    return outs[j * nb:(j + 1) * nb]
 
 
 def lib_sha256():
@@ -477,7 +525,23 @@ def fast_rank(args, world, rank, local_rank, dist):
     torch.cuda.synchronize(dev)
     n_pre = preroll(step, args.preroll, lambda: torch.cuda.synchronize(dev))
     elapsed = timed_region(step, args.steps // nb, lambda: torch.cuda.synchronize(dev), dist)
-    # kernel time: events around 16 back-to-back stitches (both plane launches) on one stream, after the
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"stitched": output_sample(last_outputs(outs, args.steps // nb, inflight, nb))}, rank)
+    result = {
+        "metric": "stitched megapixels/sec (6x4K->8K equirect, FastMapper NV12)",
+        "value": round(aggregate_mps(world, args.steps, W * H, elapsed), 1), "unit": "MP/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "preroll": {"s": args.preroll, "steps": n_pre}, "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
+        "host_issue_ms_per_step": round(ISSUE_S[0] * 1e3 / args.steps, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+        "data": "synthetic (splitmix64 frames as NV12, further sets derived by a splitmix64 key, SURVEY.md §8d rig)",
+        "config": {"workload": "F2: %d x %dx%d fullframe_fisheye -> %dx%d, vr::FastMapper::stitch_nv12 (feather, "
+                               "template without ROI), NV12 in/out" % (len(sizes), sizes[0][0], sizes[0][1], W, H),
+                   "rigs_per_gpu": 1, "frames_in_flight": inflight * nb, "streams": inflight, "frames_per_launch": nb,
+                   "frame_sets": nsets, "parallelism": "independent rig per GPU"},
+    }
+    if not args.full:
+        return result
+    # --full, kernel time: events around 16 back-to-back stitches (both plane launches) on one stream, after the
     # timed region (one frame per launch)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(stream)
@@ -492,28 +556,17 @@ def fast_rank(args, world, rank, local_rank, dist):
     lut_b, frame_b = fm.traffic_parts()
     b = lut_b / nb + frame_b  # per frame: the entries are read once per launch of nb frames
     traffic, traffic_src = pmc_traffic(args.config, 1, nb)
-    result = {
-        "metric": "stitched megapixels/sec (6x4K->8K equirect, FastMapper NV12)",
-        "value": round(aggregate_mps(world, args.steps, W * H, elapsed), 1), "unit": "MP/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "preroll": {"s": args.preroll, "steps": n_pre}, "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
-        "host_issue_ms_per_step": round(ISSUE_S[0] * 1e3 / args.steps, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-        "data": "synthetic (splitmix64 frames as NV12, further sets derived by a splitmix64 key, SURVEY.md §8d rig)",
-        "config": {"workload": "F2: %d x %dx%d fullframe_fisheye -> %dx%d, vr::FastMapper::stitch_nv12 (feather, "
-                               "template without ROI), NV12 in/out" % (len(sizes), sizes[0][0], sizes[0][1], W, H),
-                   "rigs_per_gpu": 1, "frames_in_flight": inflight * nb, "streams": inflight, "frames_per_launch": nb,
-                   "frame_sets": nsets, "parallelism": "independent rig per GPU"},
-        "roofline": {"bound": "hbm", "achieved": round(b / kern_s / 1e9, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(b / kern_s / 1e9 / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel": "fast_y_kernel + fast_uv_kernel", "kernel_us": round(kern_s * 1e6, 2),
-                     "kernel_us_basis": "torch events around 16 back-to-back frames (%d per launch) on one stream, per frame" % nb,
-                     "bytes_per_launch": b,
-                     "bytes_basis": "per (camera, 256-px run) entry block pixel 5 B (compact entry + weight; 8 B per "
-                                    "block header) or 8 B (wide planes), read once per launch of %d frames; 1.5 B out "
-                                    "per px, source bytes the weighted taps reach (octvr_fastmapper_traffic_parts)" % nb,
-                     "frac_at_step_time": round(b / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS, 4),
-                     "frac_traffic": round(traffic / kern_s / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None},
-    }
+    result["roofline"] = {
+        "bound": "hbm", "achieved": round(b / kern_s / 1e9, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+        "frac": round(b / kern_s / 1e9 / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+        "kernel": "fast_y_kernel + fast_uv_kernel", "kernel_us": round(kern_s * 1e6, 2),
+        "kernel_us_basis": "torch events around 16 back-to-back frames (%d per launch) on one stream, per frame" % nb,
+        "bytes_per_launch": b,
+        "bytes_basis": "per (camera, 256-px run) entry block pixel 5 B (compact entry + weight; 8 B per "
+                       "block header) or 8 B (wide planes), read once per launch of %d frames; 1.5 B out "
+                       "per px, source bytes the weighted taps reach (octvr_fastmapper_traffic_parts)" % nb,
+        "frac_at_step_time": round(b / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS, 4),
+        "frac_traffic": round(traffic / kern_s / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None}
     # (no cpu_baseline: F2 is not a BASELINE configuration, and the oracle's FastMapper restatement
     # rebuilds the per-rig feather weights inside every call)
     return result
@@ -632,8 +685,11 @@ def gpu_rank(args, world, rank, local_rank, dist):
     if launches == 0:  # (OCTVR_BENCH_NO_TIMING) no events: the wall time stands in
         kern_ms, launches = elapsed * 1e3, args.steps // nb
     launches *= nb  # per frame: a batched launch stitches nb frames
+    if args.dump_outputs:  # the last timed call's frames and gains, before anything else stitches
+        dump_outputs(args.dump_outputs, {"stitched": output_sample(last_outputs(outs, args.steps // nb, inflight, nb)),
+                                         "gains": np.asarray(m.gains(), np.float64)}, rank)
     serial = serial_step = None
-    if inflight > 1 and not dist:
+    if args.full and inflight > 1 and not dist:
         # supplementary, after the timed region: the composite kernel's duration with one frame in
         # flight (with two, the events on a stream also span the other stream's kernels).  The mapper
         # goes back to one slot, so no next frame's gain feed runs beside the measured composites.
@@ -662,13 +718,15 @@ def gpu_rank(args, world, rank, local_rank, dist):
     bytes_per_launch = lut_b / nb + frame_b  # per frame: the tiled LUT is read once per launch of nb frames
     avg_kernel_s = kern_ms / 1e3 / max(launches, 1)
     achieved = bytes_per_launch / avg_kernel_s / 1e9
-    n_valid = 0
-    for i in range(len(sizes)):
-        n_valid += int((mt.input(i)[3] > 0).sum())
-    survey_b_alg = 1.5 * sum(w * h for w, h in sizes) + 9.0 * n_valid + 1.5 * frame_px
-    if blend > 0:  # SURVEY.md §8d multi-band term: s16x3 Laplacian levels 1..B + f32 weight pyramids
-        f = sum(4.0 ** -l for l in range(1, int(math.ceil(math.log(blend) / math.log(2.)) - 1) + 1))
-        survey_b_alg += 12.0 * f * frame_px + 4.0 * f * n_valid
+    survey_b_alg = None
+    if args.full:  # (reads every camera's mask back from the template)
+        n_valid = 0
+        for i in range(len(sizes)):
+            n_valid += int((mt.input(i)[3] > 0).sum())
+        survey_b_alg = 1.5 * sum(w * h for w, h in sizes) + 9.0 * n_valid + 1.5 * frame_px
+        if blend > 0:  # SURVEY.md §8d multi-band term: s16x3 Laplacian levels 1..B + f32 weight pyramids
+            f = sum(4.0 ** -l for l in range(1, int(math.ceil(math.log(blend) / math.log(2.)) - 1) + 1))
+            survey_b_alg += 12.0 * f * frame_px + 4.0 * f * n_valid
 
     # HBM traffic of the dominant kernel(s) from the committed PMC summary of THIS binary and config
     # (scripts/pmc.sh + scripts/pmc_summary.py record the sha256 of the profiled liboctvr_hip.so;
@@ -719,11 +777,12 @@ def gpu_rank(args, world, rank, local_rank, dist):
                      "frac_traffic": round(traffic / avg_kernel_s / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None,
                      "traffic_over_bytes": round(traffic / bytes_per_launch, 3) if traffic else None,
                      **({"valu_busy": pmc_valu_busy(args.config)} if blend == 0 else {})},
-        "survey_b_alg": {"bytes": survey_b_alg,
-                         "gbps_at_step_time": round(survey_b_alg / (elapsed / args.steps) / 1e9, 1),
-                         "note": "SURVEY.md §8(d) B_alg (per-camera maps re-read for every valid (camera, pixel)); "
-                                 "this design moves fewer bytes for the same output, so this is a rate of the survey's "
-                                 "model, not a fraction of HBM peak"},
+        **({"survey_b_alg": {"bytes": survey_b_alg,
+                             "gbps_at_step_time": round(survey_b_alg / (elapsed / args.steps) / 1e9, 1),
+                             "note": "SURVEY.md §8(d) B_alg (per-camera maps re-read for every valid (camera, pixel)); "
+                                     "this design moves fewer bytes for the same output, so this is a rate of the "
+                                     "survey's model, not a fraction of HBM peak"}}
+           if survey_b_alg is not None else {}),
         "gains": [round(g, 6) for g in gains],
         **({"roofline_one_in_flight": {"kernel_us": round(serial * 1e6, 2),
                                         "achieved": round(bytes_per_launch / serial / 1e9, 1),
@@ -737,9 +796,9 @@ def gpu_rank(args, world, rank, local_rank, dist):
            if serial else {}),
         "mapper": m.info(),
     }
-    if rank == 0 and world == 1 and not args.no_async_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_async_e2e:
         result["async_e2e"] = async_e2e(ox, mt, sizes, W, H, blend, frames_np, dev, gain=use_gain, remap=args.remap)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(mt, frames_np, sizes, W, H, blend, gain=use_gain)
     return result
 

@@ -19,7 +19,7 @@ for rep in $(seq 1 ${REPS:-3}); do
   for cfg in ${CONFIGS:-C2}; do
     for v in ${VARIANTS:-cur}; do
       lib=; [ "$v" != cur ] && lib="OCTVR_HIP_LIB=$V/$v.so"
-      env $lib timeout -k 10 240 python bench.py --config $cfg --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-async-e2e $BENCH_ARGS \
+      env $lib timeout -k 10 240 python bench.py --config $cfg --steps ${STEPS:-30} --warmup 5 --full --no-cpu-baseline --no-async-e2e $BENCH_ARGS \
         > gpurun_out/${TAG}_${v}_${cfg}_$rep.log 2>&1 || { echo "$v $cfg rc=$?"; tail -5 gpurun_out/${TAG}_${v}_${cfg}_$rep.log; exit 1; }
       python3 -c "import json; d=json.loads(open('gpurun_out/${TAG}_${v}_${cfg}_$rep.log').read().strip().splitlines()[-1]); r=d['roofline']; o=d.get('roofline_one_in_flight',{}); print('$v $cfg $rep', d['value'], d['ms_per_step'], r['kernel_us'], o.get('kernel_us'), o.get('step_us'))"
     done

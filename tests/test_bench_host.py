@@ -122,6 +122,44 @@ def test_derived_frame_sets_match_on_device_and_host():
         assert (want != t.numpy()).mean() > 0.9
 
 
+def test_dump_outputs_sample_is_fixed_and_float(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last timed call's frames (call c writes the nb outputs of stream
+    c % inflight) as float32, whole when small, else the same seeded positions every time; gains as
+    float64; other ranks' files carry their rank."""
+    import numpy as np
+    import torch
+    import bench
+    outs = [torch.full((6, 8), v, dtype=torch.uint8) for v in range(6)]  # 3 streams x 2 frames per launch
+    assert [int(t[0, 0]) for t in bench.last_outputs(outs, 5, 3, 2)] == [2, 3]  # call 4 -> stream 1
+    assert [int(t[0, 0]) for t in bench.last_outputs(outs, 20, 3, 1)] == [1]
+    whole = bench.output_sample(outs[2:4])
+    assert whole.dtype == np.float32 and np.array_equal(whole, np.repeat([2.0, 3.0], 48))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 32)
+    big = [torch.arange(96, dtype=torch.uint8).reshape(6, 16) for _ in range(2)]
+    a, b = bench.output_sample(big), bench.output_sample([t.clone() for t in big])
+    assert a.dtype == np.float32 and a.shape == (32,) and np.array_equal(a, b)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, 192, 32))
+    assert np.array_equal(a, (idx % 96).astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "d"), {"stitched": a, "gains": np.asarray([1.0, 0.5])})
+    bench.dump_outputs(str(tmp_path / "d"), {"stitched": a}, rank=1)
+    assert sorted(os.listdir(tmp_path / "d")) == ["gains.npy", "stitched.npy", "stitched_rank1.npy"]
+    assert np.load(tmp_path / "d" / "gains.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "d" / "stitched.npy"), a)
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """Without --full the line carries only what the timed steps measure; the measurements that take runs
+    of their own (CPU baseline, async_e2e, one-in-flight kernel time) wait for --full."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 20 and a.warmup == 5
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "x"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "x"
+
+
 def test_preroll_runs_untimed_chunks_until_the_time_passes():
     """bench.preroll (the clock-settling steps before the timed region): whole
     synchronised chunks until `seconds` have passed, step indices consecutive from 0; none for 0 s."""
