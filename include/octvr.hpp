@@ -512,6 +512,17 @@ public:
         detail::check(octvr_mapper_gains(m_.get(), g.data(), n_));
         return g;
     }
+    // Pixel layouts of the inputs (all alike) and of the output of every later stitch (no reference
+    // counterpart: the reference's frames are "Y over [U|V]" only): OCTVR_PIX_YUV420P, the default, or
+    // OCTVR_PIX_NV12 (chroma rows of U,V byte pairs, what video decoders and encoders use).  Both are
+    // W x 3H/2 CV_8U images, so stitch's shape checks hold for either (octvr_hip.h
+    // octvr_mapper_set_pixel_formats).
+    void set_pixel_formats(int in_format, int out_format) {
+        detail::check(octvr_mapper_set_pixel_formats(m_.get(), in_format, out_format));
+    }
+    void pixel_formats(int& in_format, int& out_format) const {
+        detail::check(octvr_mapper_pixel_formats(m_.get(), &in_format, &out_format));
+    }
     void override_logo_option(bool option = true) { (void)option; }
     octvr_mapper* handle() const { return m_.get(); }
 

@@ -190,6 +190,21 @@ int octvr_mapper_gains(octvr_mapper* mapper, double* gains, int n);
  * multi-band / feather mappers get per-slot pyramids.  Synchronizes. */
 #define OCTVR_MAX_FRAMES_IN_FLIGHT 16
 int octvr_mapper_set_frames_in_flight(octvr_mapper* mapper, int k);
+/* Pixel layouts of the frames (no reference counterpart: the reference's frames come from ffmpeg through
+ * NPP in its own planar layout; hardware video decoders and encoders speak NV12).  Both layouts are
+ * W x 3H/2 bytes with rows [0,H) = Y:
+ *   OCTVR_PIX_YUV420P  rows [H, 3H/2): U in bytes [0, W/2), V in bytes [W/2, W)  ("Y over [U|V]", the default)
+ *   OCTVR_PIX_NV12     rows [H, 3H/2): W/2 byte pairs U,V (U first: true NV12; the FastMapper's NV12 keeps
+ *                      the reference's V,U order)
+ * in_format holds for every in_dev[i], out_format for out_dev, of every later octvr_mapper_stitch_yuv420p,
+ * octvr_mapper_stitch_batch and octvr_mapper_stitch_preview (the preview image stays RGB).  The two are
+ * independent; `pitch` rules are unchanged (>= W, any alignment).  The kernels read and write the layouts
+ * themselves (no conversion pass, no intermediate frame): the result is the planar stitch of the same
+ * pixels, bit for bit, with the chroma bytes rearranged.  Any other value: OCTVR_E_INVALID.  Synchronizes.
+ * The octvr_async_* pipeline and the FastMapper are not affected. */
+enum { OCTVR_PIX_YUV420P = 0, OCTVR_PIX_NV12 = 1 };
+int octvr_mapper_set_pixel_formats(octvr_mapper* mapper, int in_format, int out_format);
+int octvr_mapper_pixel_formats(const octvr_mapper* mapper, int* in_format, int* out_format);
 /* Algorithmic device bytes read+written by one launch of the composite (stitch) kernel: 4 B tiled
  * LUT entry (8 B in wide tiles) + 1.5 B YUV420 out per output pixel + 1.5 B per input pixel (each
  * source frame read once) + the per-item headers (multi-band / feather: the whole blend sequence). */

@@ -171,6 +171,9 @@ struct Taps {
     uint32_t fx, fy;
 };
 
+// NV12: the frame's chroma rows hold U,V byte pairs (luma column x -> bytes x & ~1 and (x & ~1) + 1) instead
+// of a U half and a V half (bytes x >> 1 and w / 2 + (x >> 1)).
+template <bool NV12 = false>
 __device__ __forceinline__ void gather_taps_frame(const SourceFrame& f, uint32_t xy, uint32_t code, Taps& t) {
     const bool valid = (code & 0x8000u) != 0;
     const TapCell tc = tap_cell(xy, f.w, f.h);
@@ -178,12 +181,13 @@ __device__ __forceinline__ void gather_taps_frame(const SourceFrame& f, uint32_t
     const int64_t p = f.pitch;
     const uint8_t* Y = f.yuv;
     const uint8_t* U = Y + (int64_t)f.h * p;
-    const uint8_t* V = U + (f.w >> 1);
+    const uint8_t* V = U + (NV12 ? 1 : (f.w >> 1));
     const int64_t r0 = (int64_t)y0 * p, r1 = (int64_t)y1 * p;
     const int64_t q0 = (int64_t)(y0 >> 1) * p, q1 = (int64_t)(y1 >> 1) * p;
+    const int k0 = NV12 ? (x0 & ~1) : (x0 >> 1), k1 = NV12 ? (x1 & ~1) : (x1 >> 1);  // chroma byte of a luma column
     const uint32_t ya = Y[r0 + x0], yb = Y[r0 + x1], yc = Y[r1 + x0], yd = Y[r1 + x1];
-    const uint32_t ua = U[q0 + (x0 >> 1)], ub = U[q0 + (x1 >> 1)], uc = U[q1 + (x0 >> 1)], ud = U[q1 + (x1 >> 1)];
-    const uint32_t va = V[q0 + (x0 >> 1)], vb = V[q0 + (x1 >> 1)], vc = V[q1 + (x0 >> 1)], vd = V[q1 + (x1 >> 1)];
+    const uint32_t ua = U[q0 + k0], ub = U[q0 + k1], uc = U[q1 + k0], ud = U[q1 + k1];
+    const uint32_t va = V[q0 + k0], vb = V[q0 + k1], vc = V[q1 + k0], vd = V[q1 + k1];
     uint32_t ca = yuv_to_rgba(ya, ua, va), cb = yuv_to_rgba(yb, ub, vb);
     uint32_t cc = yuv_to_rgba(yc, uc, vc), cd = yuv_to_rgba(yd, ud, vd);
     if (f.vig) {
@@ -239,8 +243,9 @@ __device__ __forceinline__ void tex_bilerp(uint32_t c00, uint32_t c10, uint32_t 
     for (int ch = 0; ch < 3; ch++) rgb[ch] = (uint32_t)f[ch];
 }
 
+template <bool NV12 = false>
 __device__ __forceinline__ void gather_taps(const FrameSet& fs, uint32_t xy, uint32_t code, Taps& t) {
-    gather_taps_frame(fs.f[(code >> 10) & 31u], xy, code, t);
+    gather_taps_frame<NV12>(fs.f[(code >> 10) & 31u], xy, code, t);
 }
 
 
@@ -324,7 +329,7 @@ __device__ __forceinline__ QuadOut finish_quad(const uint32_t (&rgb)[4][3], cons
 struct OutFrame {
     __amdgpu_buffer_rsrc_t rsrc;
     uint32_t pitch;
-    uint32_t u_off, v_off;  // byte offsets of the U and V planes
+    uint32_t u_off, v_off;  // byte offsets of the U and V planes; v_off = 0: an NV12 frame (U,V pairs at u_off)
 };
 constexpr uint32_t kDropOffset = 0x7FFFFFC0u;  // > any valid output byte (host: frame < 2^31 - 64 B)
 // Cache-policy bits of the output-frame stores (gfx950: 1 sc0, 2 nt, 16 sc1).  nt: streaming stores (no
@@ -333,21 +338,33 @@ constexpr uint32_t kDropOffset = 0x7FFFFFC0u;  // > any valid output byte (host:
 // were no better.
 constexpr int kOutPolicy = 2;
 
+// The output layout of a store: known at compile time (the hot instances), or the frame's own (v_off = 0)
+constexpr int kOutPlanar = 0, kOutNv12 = 1, kOutRuntime = 2;
+
+// (x, y): the quad's even top-left pixel.  NV12: the quad's U,V pair is one 16-bit store at chroma byte x.
+template <int OUT = kOutPlanar>
 __device__ __forceinline__ void store_quad(const OutFrame& o, const QuadOut& q, int x, int y, bool in) {
     const uint32_t oy = in ? (uint32_t)y * o.pitch + (uint32_t)x : kDropOffset;
     const uint32_t oc = in ? (uint32_t)(y >> 1) * o.pitch + (uint32_t)(x >> 1) : kDropOffset;
     __builtin_amdgcn_raw_buffer_store_b16((uint16_t)q.y01, o.rsrc, oy, 0, kOutPolicy);
     __builtin_amdgcn_raw_buffer_store_b16((uint16_t)q.y23, o.rsrc, in ? oy + o.pitch : kDropOffset, 0, kOutPolicy);
+    if constexpr (OUT != kOutPlanar) {
+        if (OUT == kOutNv12 || o.v_off == 0u) {
+            const uint32_t on = in ? (uint32_t)(y >> 1) * o.pitch + (uint32_t)x + o.u_off : kDropOffset;
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(q.u | q.v << 8), o.rsrc, on, 0, kOutPolicy);
+            return;
+        }
+    }
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)q.u, o.rsrc, in ? oc + o.u_off : kDropOffset, 0, kOutPolicy);
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)q.v, o.rsrc, in ? oc + o.v_off : kDropOffset, 0, kOutPolicy);
 }
 
 
-__device__ __forceinline__ OutFrame make_out_frame(uint8_t* out, int W, int H, int64_t out_pitch) {
+__device__ __forceinline__ OutFrame make_out_frame(uint8_t* out, int W, int H, int64_t out_pitch, bool nv12 = false) {
     OutFrame of;
     of.pitch = (uint32_t)out_pitch;
     of.u_off = (uint32_t)H * (uint32_t)out_pitch;
-    of.v_off = of.u_off + (uint32_t)(W >> 1);
+    of.v_off = nv12 ? 0u : of.u_off + (uint32_t)(W >> 1);
     of.rsrc = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((uint32_t)out_pitch * (uint32_t)(H + H / 2)), 0x00020000);
     return of;
 }

@@ -391,12 +391,20 @@ __device__ __forceinline__ void gain_system_row(const double* I, const int32_t* 
 // needs — the tap bytes' positions in the 8 loaded bytes as v_perm selectors, the taps' in-image flags,
 // the fractions — is derived once at issue and carried to feed_taps_finish, after every sample's loads
 // are in flight.
+//
+// NV12 frames: a tap pair's chroma is the U,V pairs at bytes c0 * 2 and c1 * 2 of ONE interleaved row, so a
+// sample takes 2 luma and 2 chroma row segments (4 loads).  The segment starts at the 4-byte aligned
+// (c0 * 2) & ~3, i.e. at an even chroma sample, so that the pair's 4 bytes lie at bytes 0-5 of it (aligned to
+// four samples as the planar segments are, a pair at samples 3 and 4 would need bytes 6-9).  Every chroma
+// row can be the frame's last row, so both starts are clamped to size - 8 (u0 / u1 hold the two segments,
+// the shifts travel in the V row shifts' bits; v0 / v1 are unused).
 struct FeedRaw {
     uint2 y0, y1, u0, u1, v0, v1;
     uint32_t sel;   // bytes of taps x0, x1: luma (bits 0-15), chroma (16-31), as v_perm selectors
     uint32_t meta;  // code bits 0-15 (fx, fy, valid), in-image ix0 ix1 iy0 iy1 at 16-19, V row shifts at 20-22 / 23-25
 };
 
+template <bool NV12 = false>
 __device__ __forceinline__ void feed_taps_issue(__amdgpu_buffer_rsrc_t rs, const SourceFrame& f, uint32_t xy,
                                                 uint32_t code, FeedRaw& r) {
     const TapCell tc = tap_cell(xy, f.w, f.h);
@@ -407,10 +415,28 @@ __device__ __forceinline__ void feed_taps_issue(__amdgpu_buffer_rsrc_t rs, const
     const uint32_t xa = x0 & ~3u, ca = c0 & ~3u;
     const uint32_t ry0 = (uint32_t)tc.y0 * p, ry1 = (uint32_t)tc.y1 * p;
     const uint32_t rc0 = (uint32_t)(tc.y0 >> 1) * p, rc1 = (uint32_t)(tc.y1 >> 1) * p;
-    const uint32_t sv0 = vo + rc0 + ca, sv1 = vo + rc1 + ca;
-    const uint32_t lv0 = min(sv0, lim), lv1 = min(sv1, lim);
     typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     u32x2 t;
+    if constexpr (NV12) {
+        const uint32_t cb = (c0 * 2u) & ~3u;  // <= w - 2: inside the row
+        const uint32_t sc0 = uo + rc0 + cb, sc1 = uo + rc1 + cb;
+        const uint32_t lc0 = min(sc0, lim), lc1 = min(sc1, lim);  // the pair's bytes stay inside the 8 loaded
+        t = __builtin_amdgcn_raw_buffer_load_b64(rs, ry0 + xa, 0, 0);
+        r.y0 = make_uint2(t.x, t.y);
+        t = __builtin_amdgcn_raw_buffer_load_b64(rs, ry1 + xa, 0, 0);
+        r.y1 = make_uint2(t.x, t.y);
+        t = __builtin_amdgcn_raw_buffer_load_b64(rs, lc0, 0, 0);
+        r.u0 = make_uint2(t.x, t.y);
+        t = __builtin_amdgcn_raw_buffer_load_b64(rs, lc1, 0, 0);
+        r.u1 = make_uint2(t.x, t.y);
+        const uint32_t iy = x0 & 3u, ic = (c0 * 2u) & 3u;  // U bytes of the two taps: ic, ic + 2 (c1 - c0)
+        r.sel = iy | (iy + (x1 - x0)) << 8 | ic << 16 | (ic + 2u * (c1 - c0)) << 24;
+        r.meta = (code & 0xFFFFu) | (tc.ix0 ? 1u << 16 : 0u) | (tc.ix1 ? 1u << 17 : 0u) | (tc.iy0 ? 1u << 18 : 0u) |
+                 (tc.iy1 ? 1u << 19 : 0u) | (sc0 - lc0) << 20 | (sc1 - lc1) << 23;
+        return;
+    }
+    const uint32_t sv0 = vo + rc0 + ca, sv1 = vo + rc1 + ca;
+    const uint32_t lv0 = min(sv0, lim), lv1 = min(sv1, lim);
     t = __builtin_amdgcn_raw_buffer_load_b64(rs, ry0 + xa, 0, 0);
     r.y0 = make_uint2(t.x, t.y);
     t = __builtin_amdgcn_raw_buffer_load_b64(rs, ry1 + xa, 0, 0);
@@ -430,14 +456,21 @@ __device__ __forceinline__ void feed_taps_issue(__amdgpu_buffer_rsrc_t rs, const
 }
 
 // Same taps, validity and conversions as gather_taps_frame (device_common.hpp), without vignette.
+template <bool NV12 = false>
 __device__ __forceinline__ void feed_taps_finish(const FeedRaw& r, Taps& t) {
     const uint32_t m = r.meta;
     const uint32_t sy = (r.sel & 0xFFFFu) | 0x0C0C0000u, sc = (r.sel >> 16) | 0x0C0C0000u;
     const uint32_t sv0 = sc + ((m >> 20) & 7u) * 0x0101u, sv1 = sc + ((m >> 23) & 7u) * 0x0101u;
     // two tap bytes of each row segment in bytes 0, 1
     const uint32_t Y0 = __builtin_amdgcn_perm(r.y0.y, r.y0.x, sy), Y1 = __builtin_amdgcn_perm(r.y1.y, r.y1.x, sy);
-    const uint32_t U0 = __builtin_amdgcn_perm(r.u0.y, r.u0.x, sc), U1 = __builtin_amdgcn_perm(r.u1.y, r.u1.x, sc);
-    const uint32_t V0 = __builtin_amdgcn_perm(r.v0.y, r.v0.x, sv0), V1 = __builtin_amdgcn_perm(r.v1.y, r.v1.x, sv1);
+    uint32_t U0, U1, V0, V1;
+    if constexpr (NV12) {  // sv0 / sv1: the U bytes in the (clamped) interleaved segments; V is the next byte
+        U0 = __builtin_amdgcn_perm(r.u0.y, r.u0.x, sv0), U1 = __builtin_amdgcn_perm(r.u1.y, r.u1.x, sv1);
+        V0 = __builtin_amdgcn_perm(r.u0.y, r.u0.x, sv0 + 0x0101u), V1 = __builtin_amdgcn_perm(r.u1.y, r.u1.x, sv1 + 0x0101u);
+    } else {
+        U0 = __builtin_amdgcn_perm(r.u0.y, r.u0.x, sc), U1 = __builtin_amdgcn_perm(r.u1.y, r.u1.x, sc);
+        V0 = __builtin_amdgcn_perm(r.v0.y, r.v0.x, sv0), V1 = __builtin_amdgcn_perm(r.v1.y, r.v1.x, sv1);
+    }
     uint32_t ca, cb, cc, cd;
     yuv_pair_to_rgba(Y0, U0, V0, ca, cb);
     yuv_pair_to_rgba(Y1, U1, V1, cc, cd);
@@ -470,7 +503,7 @@ __device__ __forceinline__ void sample_rgb(const Taps& t, int tex, uint32_t (&rg
 typedef __attribute__((address_space(4))) const SourceFrame kSourceFrame;
 static_assert(offsetof(FeedBatch<1>, src) == 0 && offsetof(FeedBatch<4>, src) == 0, "FeedBatch layout");
 
-template <bool LEAN, int NF>
+template <bool LEAN, int NF, bool NV12>
 __device__ __forceinline__ void gain_feed_body(const CompositeEntry* samples, const uint16_t* partners, int tex,
                                                int n_chunks, const int32_t* N, int n) {
     typedef __attribute__((address_space(4))) const FeedBatch<NF> kFeedBatch;
@@ -523,13 +556,13 @@ __device__ __forceinline__ void gain_feed_body(const CompositeEntry* samples, co
             Taps t[kLeanBatch];
             if (fr.vig || tex) {  // vignette / clamped texture taps: per-tap byte gathers
 #pragma unroll
-                for (int u = 0; u < kLeanBatch; u++) gather_taps_frame(fr, e[u].xy, e[u].code, t[u]);
+                for (int u = 0; u < kLeanBatch; u++) gather_taps_frame<NV12>(fr, e[u].xy, e[u].code, t[u]);
             } else {
                 FeedRaw raw[kLeanBatch];
 #pragma unroll
-                for (int u = 0; u < kLeanBatch; u++) feed_taps_issue(rs, fr, e[u].xy, e[u].code, raw[u]);
+                for (int u = 0; u < kLeanBatch; u++) feed_taps_issue<NV12>(rs, fr, e[u].xy, e[u].code, raw[u]);
 #pragma unroll
-                for (int u = 0; u < kLeanBatch; u++) feed_taps_finish(raw[u], t[u]);
+                for (int u = 0; u < kLeanBatch; u++) feed_taps_finish<NV12>(raw[u], t[u]);
             }
             double nv[kLeanBatch];
             uint32_t pm_any = 0u;
@@ -569,13 +602,13 @@ __device__ __forceinline__ void gain_feed_body(const CompositeEntry* samples, co
         }
         if (fr.vig || tex) {  // vignette / clamped texture taps: per-tap byte gathers
 #pragma unroll
-            for (int u = 0; u < kPer; u++) gather_taps_frame(fr, es[u].xy, es[u].code, t[u]);
+            for (int u = 0; u < kPer; u++) gather_taps_frame<NV12>(fr, es[u].xy, es[u].code, t[u]);
         } else {
             FeedRaw raw[kPer];
 #pragma unroll
-            for (int u = 0; u < kPer; u++) feed_taps_issue(rs, fr, es[u].xy, es[u].code, raw[u]);
+            for (int u = 0; u < kPer; u++) feed_taps_issue<NV12>(rs, fr, es[u].xy, es[u].code, raw[u]);
 #pragma unroll
-            for (int u = 0; u < kPer; u++) feed_taps_finish(raw[u], t[u]);
+            for (int u = 0; u < kPer; u++) feed_taps_finish<NV12>(raw[u], t[u]);
         }
 #pragma unroll
         for (int u = 0; u < kPer; u++) {
@@ -656,22 +689,23 @@ __device__ __forceinline__ void gain_feed_body(const CompositeEntry* samples, co
     if (tid < n) gains[tid] = ok ? s_x[tid] : 1.0;  // cv::solve failure leaves gains_ unspecified; 1 as the oracle
 }
 
-template <int NF>
+// NV12: the frames' chroma rows are U,V pairs (kPixInNv12)
+template <int NF, bool NV12 = false>
 __global__ void __launch_bounds__(256) gain_feed_kernel(FeedBatch<NF> batch, const CompositeEntry* samples,
                                                         const uint16_t* partners, int tex, int n_chunks, const int32_t* N,
                                                         int n) {
     (void)batch;  // read through the kernarg segment (kFeedBatch)
-    gain_feed_body<false, NF>(samples, partners, tex, n_chunks, N, n);
+    gain_feed_body<false, NF, NV12>(samples, partners, tex, n_chunks, N, n);
 }
-template <int NF>
+template <int NF, bool NV12 = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(80)))
 gain_feed_lean_kernel(FeedBatch<NF> batch, const CompositeEntry* samples, const uint16_t* partners, int tex, int n_chunks,
                       const int32_t* N, int n) {
     (void)batch;
-    gain_feed_body<true, NF>(samples, partners, tex, n_chunks, N, n);
+    gain_feed_body<true, NF, NV12>(samples, partners, tex, n_chunks, N, n);
 }
 
-template <int NF>
+template <int NF, bool NV12>
 static void launch_feed_nf(const FrameSet* frames, const CompositeEntry* samples, const uint16_t* partners, int tex,
                            int n_chunks, const int32_t* N, int n, unsigned long long* const* totals,
                            uint32_t* const* tickets, double* const* gains, hipStream_t s, bool lean) {
@@ -684,32 +718,39 @@ static void launch_feed_nf(const FrameSet* frames, const CompositeEntry* samples
         fb.gains[f] = gains[f];
     }
     if (lean)
-        hipLaunchKernelGGL(gain_feed_lean_kernel<NF>, dim3(n_chunks * NF), dim3(256), 0, s, fb, samples, partners, tex,
+        hipLaunchKernelGGL((gain_feed_lean_kernel<NF, NV12>), dim3(n_chunks * NF), dim3(256), 0, s, fb, samples, partners, tex,
                            n_chunks, N, n);
     else
-        hipLaunchKernelGGL(gain_feed_kernel<NF>, dim3(n_chunks * NF), dim3(256), 0, s, fb, samples, partners, tex,
+        hipLaunchKernelGGL((gain_feed_kernel<NF, NV12>), dim3(n_chunks * NF), dim3(256), 0, s, fb, samples, partners, tex,
                            n_chunks, N, n);
 }
 
 hipError_t launch_gain_feed_batch(const FrameSet* frames, int nf, const CompositeEntry* samples, const uint16_t* partners,
                                   int tex, int n_chunks, const int32_t* N, int n, unsigned long long* const* totals,
-                                  uint32_t* const* tickets, double* const* gains, hipStream_t s, bool lean) {
+                                  uint32_t* const* tickets, double* const* gains, hipStream_t s, bool lean, int pix) {
     if (n_chunks <= 0 || n > kGainMaxCams) return hipErrorInvalidValue;
-    if (nf == 1)
-        launch_feed_nf<1>(frames, samples, partners, tex, n_chunks, N, n, totals, tickets, gains, s, lean);
+    if (nf != 1 && nf != 2 && nf != 4) return hipErrorInvalidValue;
+    if (pix & kPixInNv12) {
+        if (nf == 1)
+            launch_feed_nf<1, true>(frames, samples, partners, tex, n_chunks, N, n, totals, tickets, gains, s, lean);
+        else if (nf == 2)
+            launch_feed_nf<2, true>(frames, samples, partners, tex, n_chunks, N, n, totals, tickets, gains, s, lean);
+        else
+            launch_feed_nf<4, true>(frames, samples, partners, tex, n_chunks, N, n, totals, tickets, gains, s, lean);
+    } else if (nf == 1)
+        launch_feed_nf<1, false>(frames, samples, partners, tex, n_chunks, N, n, totals, tickets, gains, s, lean);
     else if (nf == 2)
-        launch_feed_nf<2>(frames, samples, partners, tex, n_chunks, N, n, totals, tickets, gains, s, lean);
-    else if (nf == 4)
-        launch_feed_nf<4>(frames, samples, partners, tex, n_chunks, N, n, totals, tickets, gains, s, lean);
+        launch_feed_nf<2, false>(frames, samples, partners, tex, n_chunks, N, n, totals, tickets, gains, s, lean);
     else
-        return hipErrorInvalidValue;
+        launch_feed_nf<4, false>(frames, samples, partners, tex, n_chunks, N, n, totals, tickets, gains, s, lean);
     return hipGetLastError();
 }
 
 hipError_t launch_gain_feed(const FrameSet& frames, const CompositeEntry* samples, const uint16_t* partners, int tex,
                             int n_chunks, const int32_t* N, int n,
-                            unsigned long long* totals, uint32_t* tickets, double* gains, hipStream_t s, bool lean) {
-    return launch_gain_feed_batch(&frames, 1, samples, partners, tex, n_chunks, N, n, &totals, &tickets, &gains, s, lean);
+                            unsigned long long* totals, uint32_t* tickets, double* gains, hipStream_t s, bool lean, int pix) {
+    return launch_gain_feed_batch(&frames, 1, samples, partners, tex, n_chunks, N, n, &totals, &tickets, &gains, s, lean,
+                                  pix);
 }
 
 struct GainArgs {
@@ -803,6 +844,11 @@ struct StageGroup {
 // The loaded bytes are only touched in stage_store (an iteration later): a select on them right
 // after the load would make the compiler wait for the load in the iteration that issues it.
 constexpr uint32_t kStageBlack = 1u, kStageNoVig = 2u;
+// kStageNv12 (IN = kInRuntime only): uq / vq hold the group's 8 interleaved chroma bytes (U,V pairs 0-1, 2-3)
+constexpr uint32_t kStageNv12 = 4u;
+// The input layout of a staging instance: known at compile time (the planar instances and the hot NV12 ones),
+// or the launch's (`pix`, wave-uniform: the instances of the colder mapper kinds)
+constexpr int kInPlanar = 0, kInNv12 = 1, kInRuntime = 2;
 
 // Metadata of a staged item as the waves hold it: one 16-byte load by 5 lanes (lane 0 the TileHdr,
 // lane 1 + q slot q's TileSlot), decoded with v_readlane on demand (a uniform lane index), so the
@@ -863,8 +909,11 @@ __device__ __forceinline__ StageSlot stage_slot(const TileMeta& m, int t_end, in
 // box rows' tap spans.  Invalid groups (a slot's last chunk, chunks past the item's) read the box origin
 // and are marked dst = -1.  With box columns 8-aligned, the Y load is 8-byte and the U / V loads 4-byte
 // aligned (DWORD_STAGE).  Offsets use 24-bit multiplies: rows < 256, pitch < 2^24 (checked on the host).
-template <bool DWORD_STAGE, bool VIG>
-__device__ __forceinline__ void stage_load(const StageSlot& s, uint32_t stride, uint32_t g, StageGroup& sg) {
+// NV12 frames (IN, nv12): the group's 4 U,V pairs are the 8 bytes at the group's own column of the chroma row
+// (8-byte aligned where the Y load is): ONE 8-byte load, its low dword in uq (pairs 0, 1), its high in vq.
+template <bool DWORD_STAGE, bool VIG, int IN = kInPlanar>
+__device__ __forceinline__ void stage_load(const StageSlot& s, uint32_t stride, uint32_t g, StageGroup& sg,
+                                           bool nv12 = false) {
     const bool ok = s.live && (g & kGroupValid) != 0u;
     const uint32_t row_k = ok ? (g & 255u) : 0u, col_k = ok ? (g >> 8) & 31u : 0u;
     const SourceFrame& f = s.f;
@@ -878,7 +927,23 @@ __device__ __forceinline__ void stage_load(const StageSlot& s, uint32_t stride, 
     const gu8* Ub = base + (int64_t)(f.h + (int)(s.by0 >> 1)) * f.pitch + (s.bx0 >> 1);
     const gu8* Vb = Ub + (f.w >> 1);
     const uint32_t oy = __umul24(row, p32) + col * 8u, oc = __umul24(row >> 1, p32) + col * 4u;
-    if (DWORD_STAGE) {
+    if (IN == kInNv12 || (IN == kInRuntime && nv12)) {
+        const gu8* Cp = base + (int64_t)(f.h + (int)(s.by0 >> 1)) * f.pitch + s.bx0 + (oc + col * 4u);
+        if (DWORD_STAGE) {
+            const uint64_t yy = *(const gu64*)(Yb + oy);
+            const uint64_t cc = *(const gu64*)Cp;
+            sg.y0 = (uint32_t)yy;
+            sg.y1 = (uint32_t)(yy >> 32);
+            sg.uq = (uint32_t)cc;
+            sg.vq = (uint32_t)(cc >> 32);
+        } else {
+            const gu8* Yp = Yb + oy;
+            sg.y0 = (uint32_t)Yp[0] | ((uint32_t)Yp[1] << 8) | ((uint32_t)Yp[2] << 16) | ((uint32_t)Yp[3] << 24);
+            sg.y1 = (uint32_t)Yp[4] | ((uint32_t)Yp[5] << 8) | ((uint32_t)Yp[6] << 16) | ((uint32_t)Yp[7] << 24);
+            sg.uq = (uint32_t)Cp[0] | ((uint32_t)Cp[1] << 8) | ((uint32_t)Cp[2] << 16) | ((uint32_t)Cp[3] << 24);
+            sg.vq = (uint32_t)Cp[4] | ((uint32_t)Cp[5] << 8) | ((uint32_t)Cp[6] << 16) | ((uint32_t)Cp[7] << 24);
+        }
+    } else if (DWORD_STAGE) {
         const uint64_t yy = *(const gu64*)(Yb + oy);
         sg.y0 = (uint32_t)yy;
         sg.y1 = (uint32_t)(yy >> 32);
@@ -894,6 +959,7 @@ __device__ __forceinline__ void stage_load(const StageSlot& s, uint32_t stride, 
         sg.vq = (uint32_t)Vp[0] | ((uint32_t)Vp[1] << 8) | ((uint32_t)Vp[2] << 16) | ((uint32_t)Vp[3] << 24);
     }
     sg.flags = img ? 0u : kStageBlack;
+    if (IN == kInRuntime && nv12) sg.flags |= kStageNv12;
     sg.dst = ok ? (int32_t)(s.lds + __umul24(row_k, stride) + col_k * 8u) : -1;
     if (VIG) {  // 8 gains (32-byte aligned: w % 8 == 0); a camera without vignette uses 1.0 gains
         const float* gv = f.vig ? f.vig + (int64_t)(s.by0 + row) * f.w + s.bx0 + col * 8u
@@ -916,19 +982,31 @@ __device__ __forceinline__ uint16_t group_issue(const __amdgpu_buffer_rsrc_t& gr
                                                 (uint32_t)uniform(tt) * (uint32_t)(kGroupFirst * 64 * 2), 0);
 }
 
-template <bool VIG>
+template <bool VIG, int IN = kInPlanar>
 __device__ __forceinline__ void stage_store(const StageGroup& sg, uint32_t* s_rgb) {
     if (sg.dst < 0) return;
     const bool black = (sg.flags & kStageBlack) != 0;  // Y = 0, U = V = 128 -> RGBA 0
     const uint32_t y0 = black ? 0u : sg.y0, y1 = black ? 0u : sg.y1;
     // chroma bytes xor 0x80 read as signed bytes are u - 128: one v_cvt_f32_i32_sdwa (sext) each
-    const uint32_t uq = black ? 0u : sg.uq ^ 0x80808080u, vq = black ? 0u : sg.vq ^ 0x80808080u;
+    uint32_t uq = black ? 0u : sg.uq ^ 0x80808080u, vq = black ? 0u : sg.vq ^ 0x80808080u;
     auto ch = [](uint32_t w, int k) { return (float)(signed char)((w >> (8 * k)) & 255u); };
     uint4 a, b;
-    yuv2_to_rgba_c(y0 & 255u, (y0 >> 8) & 255u, ch(uq, 0), ch(vq, 0), a.x, a.y);
-    yuv2_to_rgba_c((y0 >> 16) & 255u, y0 >> 24, ch(uq, 1), ch(vq, 1), a.z, a.w);
-    yuv2_to_rgba_c(y1 & 255u, (y1 >> 8) & 255u, ch(uq, 2), ch(vq, 2), b.x, b.y);
-    yuv2_to_rgba_c((y1 >> 16) & 255u, y1 >> 24, ch(uq, 3), ch(vq, 3), b.z, b.w);
+    if constexpr (IN == kInNv12) {  // uq = U0 V0 U1 V1, vq = U2 V2 U3 V3
+        yuv2_to_rgba_c(y0 & 255u, (y0 >> 8) & 255u, ch(uq, 0), ch(uq, 1), a.x, a.y);
+        yuv2_to_rgba_c((y0 >> 16) & 255u, y0 >> 24, ch(uq, 2), ch(uq, 3), a.z, a.w);
+        yuv2_to_rgba_c(y1 & 255u, (y1 >> 8) & 255u, ch(vq, 0), ch(vq, 1), b.x, b.y);
+        yuv2_to_rgba_c((y1 >> 16) & 255u, y1 >> 24, ch(vq, 2), ch(vq, 3), b.z, b.w);
+    } else {
+        if (IN == kInRuntime && (sg.flags & kStageNv12)) {  // de-interleave: two v_perm_b32
+            const uint32_t lo = uq, hi = vq;
+            uq = __builtin_amdgcn_perm(hi, lo, 0x06040200u);
+            vq = __builtin_amdgcn_perm(hi, lo, 0x07050301u);
+        }
+        yuv2_to_rgba_c(y0 & 255u, (y0 >> 8) & 255u, ch(uq, 0), ch(vq, 0), a.x, a.y);
+        yuv2_to_rgba_c((y0 >> 16) & 255u, y0 >> 24, ch(uq, 1), ch(vq, 1), a.z, a.w);
+        yuv2_to_rgba_c(y1 & 255u, (y1 >> 8) & 255u, ch(uq, 2), ch(vq, 2), b.x, b.y);
+        yuv2_to_rgba_c((y1 >> 16) & 255u, y1 >> 24, ch(uq, 3), ch(vq, 3), b.z, b.w);
+    }
     if (VIG && !(sg.flags & kStageNoVig)) {
         a.x = vig_mul(a.x, sg.g0.x);
         a.y = vig_mul(a.y, sg.g0.y);
@@ -1009,9 +1087,9 @@ struct TileData {
 // scalar byte offset, so no per-lane 64-bit address is formed per item (TiledLutDev::upload checks
 // that the entries fit 32-bit offsets)
 // E24: the lane's four 24-bit entries of each half (tiled_entry24) as three dwords (d.e4[h].w unused)
-template <bool DWORD_STAGE, bool VIG, bool E24>
+template <bool DWORD_STAGE, bool VIG, bool E24, int IN = kInPlanar>
 __device__ __forceinline__ void data_issue(const __amdgpu_buffer_rsrc_t& er, const TileMeta& m, int t_end, int lg,
-                                           const StageSlot& sl, uint32_t g, TileData& d) {
+                                           const StageSlot& sl, uint32_t g, TileData& d, bool nv12 = false) {
     const bool live = m.t < t_end;
     const int tid = threadIdx.x;
 #pragma unroll
@@ -1032,7 +1110,7 @@ __device__ __forceinline__ void data_issue(const __amdgpu_buffer_rsrc_t& er, con
         d.sg.dst = -1;
         return;
     }
-    stage_load<DWORD_STAGE, VIG>(sl, m.stride & ((1u << kStrideBits) - 1u), g, d.sg);
+    stage_load<DWORD_STAGE, VIG, IN>(sl, m.stride & ((1u << kStrideBits) - 1u), g, d.sg, nv12);
 }
 
 // The composite's two sinks.  MODE 0: gain + RGB -> YUV420P into the output frame (blend = 0).
@@ -1074,6 +1152,7 @@ __device__ __forceinline__ OutFrame make_result_frame(const RgbaOut& r) {
 // A deep level-0 quad's final result straight from the remap (mb_blend level 0 for owned = 4: R = G0,
 // convertTo(CV_8UC3) into result(align_result_roi) and RGB -> YUV420P, or the RGBA result image of a
 // scaled output).  q holds the quad's four packed RGB pixels; (x, y): the quad on the level-0 grid.
+template <int OUT = kOutPlanar>
 __device__ __forceinline__ void store_result(const OutFrame& o, bool rgba, const QuadOut& q, int x, int y, bool in) {
     if (rgba) {
         typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -1083,7 +1162,7 @@ __device__ __forceinline__ void store_result(const OutFrame& o, bool rgba, const
         return;
     }
     const uint32_t px[4] = {q.y01, q.y23, q.u, q.v};
-    store_quad(o, quad_yuv(px), x, y, in);
+    store_quad<OUT>(o, quad_yuv(px), x, y, in);
 }
 
 __device__ __forceinline__ void store_rgba(const RgbaSink& o, const QuadOut& q, uint32_t cam, int x, int y, bool in) {
@@ -1107,15 +1186,15 @@ __device__ __forceinline__ void store_rgba(const RgbaSink& o, const QuadOut& q, 
 // One half of an item: MODE 0 the YUV quad into `of`; MODE 1 the G0 quad where the item's flags say some
 // pyrDown or blend reads the lane's sub-tile (item_g0_bit), and the final result into `of` (the result frame)
 // where they say the sub-tile is deep (item_result_bit).  The lane's sub-tile: quarter (lane & 63) >> 4.
-template <int MODE>
+template <int MODE, int OUT = kOutPlanar>
 __device__ __forceinline__ void store_half(const OutFrame& of, const RgbaSink& ro, bool res_rgba, const QuadOut& q,
                                            uint32_t cam, uint32_t flags, int h, int x, int y, bool in) {
     if constexpr (MODE == 0) {
-        store_quad(of, q, x, y, in);
+        store_quad<OUT>(of, q, x, y, in);
     } else {
         const int q4 = (int)((threadIdx.x & 63u) >> 4);
         if (flags & item_g0_bit(h, q4)) store_rgba(ro, q, cam, x, y, in);
-        if (flags & item_result_bit(h, q4)) store_result(of, res_rgba, q, x, y, in);
+        if (flags & item_result_bit(h, q4)) store_result<OUT>(of, res_rgba, q, x, y, in);
     }
 }
 
@@ -1150,9 +1229,17 @@ __device__ __forceinline__ uint32_t tap_off(uint32_t e) { return (e >> 13) & 0x3
 // TEX: texture-convention entries (tiled_entry_tex): the taps as usual, the texture filter model instead of
 // the weight table.
 // LG: 1 << LG frames per launch (FrameBatch; MODE 0 only)
-template <bool DWORD_STAGE, int MODE, bool VIG, bool TEX, int LG, bool E24>
+// PF: the pixel layouts.  kPfPlanar: "Y over [U|V]" in and out.  kPfNv12: NV12 in and out, compiled in (the hot
+// instances: two 8-byte loads per staging group, one 16-bit chroma store per quad).  kPfRuntime: the launch's
+// `pix` (kPixInNv12 | kPixOutNv12), wave-uniform branches: mixed layouts and the colder mapper kinds.
+constexpr int kPfPlanar = 0, kPfNv12 = 3, kPfRuntime = 4;
+template <bool DWORD_STAGE, int MODE, bool VIG, bool TEX, int LG, bool E24, int PF = kPfPlanar>
 __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& frames, TiledLut lut, int W, int H, int use_gain,
-                                                  int64_t out_pitch, RgbaOut rgba) {
+                                                  int64_t out_pitch, RgbaOut rgba, int pix = 0) {
+    constexpr int IN = PF == kPfRuntime ? kInRuntime : PF == kPfNv12 ? kInNv12 : kInPlanar;
+    constexpr int OUT = PF == kPfRuntime ? kOutRuntime : PF == kPfNv12 ? kOutNv12 : kOutPlanar;
+    const bool in_nv12 = IN == kInRuntime ? (pix & kPixInNv12) != 0 : IN == kInNv12;
+    const bool out_nv12 = OUT == kOutRuntime ? (pix & kPixOutNv12) != 0 : OUT == kOutNv12;
     __shared__ StitchLds L;
     extern __shared__ __attribute__((aligned(16))) uint2 s_wtab[];  // 1,024 weight pairs at LDS 0x4000
     uint32_t* const s_rgb = L.rgb;
@@ -1188,7 +1275,7 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
     bool res_rgba = false;
     const int out_bytes = (int)((uint32_t)out_pitch * (uint32_t)(H + H / 2));
     if constexpr (MODE == 0) {
-        of = make_out_frame(kernarg_out<1 << LG>(0), W, H, out_pitch);
+        of = make_out_frame(kernarg_out<1 << LG>(0), W, H, out_pitch, out_nv12);
     } else {
         ro = RgbaSink{__builtin_amdgcn_make_buffer_rsrc(rgba.base, 0, (int)rgba.bytes, 0x00020000), rgba.cams};
         of = make_result_frame(rgba);
@@ -1218,7 +1305,7 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
     const uint32_t g0 = group_issue(grsrc, t0, t_end, lg);
     __syncthreads();
     TileData d;
-    data_issue<DWORD_STAGE, VIG, E24>(ersrc, cur, t_end, lg, stage_slot<true>(cur, t_end, wave), g0, d);
+    data_issue<DWORD_STAGE, VIG, E24, IN>(ersrc, cur, t_end, lg, stage_slot<true>(cur, t_end, wave), g0, d, in_nv12);
     int t_mv = t0 + step < t_end ? t0 + step : t_end;  // item of the metadata in flight (mv)
     int t_n2 = t_mv < t_end && t0 + 2 * step < t_end ? t0 + 2 * step : t_end;  // item after it
     uint4 mv = meta_issue(mrsrc, t_mv, t_end, lg);
@@ -1245,7 +1332,9 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
     int px = 0, py = 0;  // the previous item's quad of this lane in its first half
     // MODE 0 stores of items wholly inside the frame: the lane's part of the byte offsets is
     // loop-invariant (voffset), the item's part a scalar (soffset) — no per-lane address arithmetic
-    const uint32_t lane_y = (uint32_t)(2 * qy) * of.pitch + (uint32_t)(2 * qx), lane_c = (uint32_t)qy * of.pitch + (uint32_t)qx;
+    // (NV12: the lane's U,V pair at chroma byte 2 qx)
+    const uint32_t lane_y = (uint32_t)(2 * qy) * of.pitch + (uint32_t)(2 * qx),
+                   lane_c = (uint32_t)qy * of.pitch + (uint32_t)(out_nv12 ? 2 * qx : qx);
     int pox = 0, poy = 0;  // the previous item's origin (uniform)
     bool pfull = false;    // the previous item lies wholly inside W x H (uniform)
     uint32_t pcam = 0, pfl = 0;  // the previous item's RGBA-mode camera and flags (item_result_bit / item_g0_bit)
@@ -1271,7 +1360,7 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
             if (tid < kTileSlots) s_slot_gain[tid] = f32x2_t{gc, gc};
         }
         if (claimed && tid == 0) s_claim[par] = claim;  // issued one iteration ago
-        stage_store<VIG>(d.sg, s_rgb);
+        stage_store<VIG, IN>(d.sg, s_rgb);
         const uint32_t nch = (cur.nslots >> 8) & 0xFFu;
         if (nch > (uint32_t)kGroupFirst) {  // large items only: the other chunks now, groups from grp1
             const uint32_t ovf = cur.stride >> kStrideBits;
@@ -1279,8 +1368,8 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
                 const uint32_t gk = __builtin_amdgcn_raw_buffer_load_b16(
                     g1rsrc, (uint32_t)(tid & 63) * 2u, (ovf + (uint32_t)(c - kGroupFirst)) * 128u, 0);
                 StageGroup sg;
-                stage_load<DWORD_STAGE, VIG>(stage_slot(cur, t_end, c), S, gk, sg);
-                stage_store<VIG>(sg, s_rgb);
+                stage_load<DWORD_STAGE, VIG, IN>(stage_slot(cur, t_end, c), S, gk, sg, in_nv12);
+                stage_store<VIG, IN>(sg, s_rgb);
             }
         }
         __syncthreads();
@@ -1302,19 +1391,25 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
 #pragma unroll
             for (int h = 0; h < kItemHalves; h++) {
                 const uint32_t sy = (uint32_t)uniform((poy + h * kTileH) * (int)of.pitch + pox);
-                const uint32_t sc = (uint32_t)uniform(((poy + h * kTileH) >> 1) * (int)of.pitch + (pox >> 1));
+                const uint32_t sc =
+                    (uint32_t)uniform(((poy + h * kTileH) >> 1) * (int)of.pitch + (out_nv12 ? pox : pox >> 1));
                 __builtin_amdgcn_raw_buffer_store_b16((uint16_t)prev[h].y01, of.rsrc, lane_y, sy, kOutPolicy);
                 __builtin_amdgcn_raw_buffer_store_b16((uint16_t)prev[h].y23, of.rsrc, lane_y, sy + of.pitch, kOutPolicy);
-                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)prev[h].u, of.rsrc, lane_c, sc + of.u_off, kOutPolicy);
-                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)prev[h].v, of.rsrc, lane_c, sc + of.v_off, kOutPolicy);
+                if (out_nv12) {  // (a constant in the compiled-in instances, else wave-uniform)
+                    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(prev[h].u | prev[h].v << 8), of.rsrc, lane_c,
+                                                          sc + of.u_off, kOutPolicy);
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)prev[h].u, of.rsrc, lane_c, sc + of.u_off, kOutPolicy);
+                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)prev[h].v, of.rsrc, lane_c, sc + of.v_off, kOutPolicy);
+                }
             }
         } else {
 #pragma unroll
             for (int h = 0; h < kItemHalves; h++)
-                store_half<MODE>(of, ro, res_rgba, prev[h], pcam, pfl, h, px, py + h * kTileH, pin && py + h * kTileH < H);
+                store_half<MODE, OUT>(of, ro, res_rgba, prev[h], pcam, pfl, h, px, py + h * kTileH, pin && py + h * kTileH < H);
         }
         // the next item's first staging slot resolved only now (short scalar live ranges), then its loads
-        data_issue<DWORD_STAGE, VIG, E24>(ersrc, nxt, t_end, lg, stage_slot<true>(nxt, t_end, wave), mg, d);
+        data_issue<DWORD_STAGE, VIG, E24, IN>(ersrc, nxt, t_end, lg, stage_slot<true>(nxt, t_end, wave), mg, d, in_nv12);
         mv = meta_issue(mrsrc, t_n2, t_end, lg);
         mg = group_issue(grsrc, t_n2, t_end, lg);
         t_mv = t_n2;
@@ -1385,14 +1480,25 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
     if (MODE == 0 && lg) of.rsrc = __builtin_amdgcn_make_buffer_rsrc(kernarg_out<1 << LG>(pfr), 0, out_bytes, 0x00020000);
 #pragma unroll
     for (int h = 0; h < kItemHalves; h++)
-        store_half<MODE>(of, ro, res_rgba, prev[h], pcam, pfl, h, px, py + h * kTileH, pin && py + h * kTileH < H);
+        store_half<MODE, OUT>(of, ro, res_rgba, prev[h], pcam, pfl, h, px, py + h * kTileH, pin && py + h * kTileH < H);
 }
 
-template <bool DWORD_STAGE, int MODE, bool VIG, int LG, bool E24>
+// PF: kPfPlanar or kPfNv12 (compiled in)
+template <bool DWORD_STAGE, int MODE, bool VIG, int LG, bool E24, int PF = kPfPlanar>
 __global__ void __launch_bounds__(256, kStitchRegBlocks) __attribute__((amdgpu_num_sgpr(kStitchSgprs)))
 __attribute__((amdgpu_num_vgpr(kStitchVgprs))) stitch_tiled_kernel(FrameBatch<1 << LG> frames, TiledLut lut, int W, int H,
                                                                    int use_gain, int64_t out_pitch, RgbaOut rgba) {
-    stitch_tiled_body<DWORD_STAGE, MODE, VIG, false, LG, E24>(frames, lut, W, H, use_gain, out_pitch, rgba);
+    stitch_tiled_body<DWORD_STAGE, MODE, VIG, false, LG, E24, PF>(frames, lut, W, H, use_gain, out_pitch, rgba);
+}
+// The instance of every other launch with an NV12 side: the layouts from `pix` (kPfRuntime), byte-wise staging
+// (any alignment) and the vignette path (cameras without one stage with kStageNoVig), at the texture
+// instance's register budget.  No conversion pass either: the same kernel reads and writes the layouts itself.
+template <int MODE, bool TEX, int LG, bool E24>
+__global__ void __launch_bounds__(256, kStitchTexRegBlocks) __attribute__((amdgpu_num_sgpr(kStitchSgprs)))
+__attribute__((amdgpu_num_vgpr(kStitchTexVgprs))) stitch_tiled_pix_kernel(FrameBatch<1 << LG> frames, TiledLut lut, int W,
+                                                                          int H, int use_gain, int64_t out_pitch,
+                                                                          RgbaOut rgba, int pix) {
+    stitch_tiled_body<false, MODE, true, TEX, LG, E24, kPfRuntime>(frames, lut, W, H, use_gain, out_pitch, rgba, pix);
 }
 template <bool DWORD_STAGE, int MODE, bool VIG, int LG>
 __global__ void __launch_bounds__(256, kStitchTexRegBlocks) __attribute__((amdgpu_num_sgpr(kStitchSgprs)))
@@ -1406,7 +1512,7 @@ __attribute__((amdgpu_num_vgpr(kStitchTexVgprs))) stitch_tiled_tex_kernel(FrameB
 template <int MODE>
 __global__ void __launch_bounds__(256) stitch_wide_kernel(FrameSet frames, TiledLut lut, int W, int H,
                                                           const double* gains, int use_gain, uint8_t* out,
-                                                          int64_t out_pitch, RgbaOut rgba) {
+                                                          int64_t out_pitch, RgbaOut rgba, int pix) {
     __shared__ float s_gain[kMaxCams];
     const int tid = threadIdx.x;
     if (tid < kMaxCams) s_gain[tid] = use_gain ? (float)gains[tid] : 1.0f;
@@ -1414,7 +1520,7 @@ __global__ void __launch_bounds__(256) stitch_wide_kernel(FrameSet frames, Tiled
     OutFrame of{};
     RgbaSink ro{};
     if constexpr (MODE == 0) {
-        of = make_out_frame(out, W, H, out_pitch);
+        of = make_out_frame(out, W, H, out_pitch, (pix & kPixOutNv12) != 0);
     } else {
         ro = RgbaSink{__builtin_amdgcn_make_buffer_rsrc(rgba.base, 0, (int)rgba.bytes, 0x00020000), rgba.cams};
         of = make_result_frame(rgba);
@@ -1427,7 +1533,12 @@ __global__ void __launch_bounds__(256) stitch_wide_kernel(FrameSet frames, Tiled
     const uint32_t cd[4] = {e0.y, e0.w, e1.y, e1.w};
     Taps tp[4];
 #pragma unroll
-    for (int p = 0; p < 4; p++) gather_taps(frames, xy[p], cd[p], tp[p]);
+    for (int p = 0; p < 4; p++) {
+        if (pix & kPixInNv12)  // uniform
+            gather_taps<true>(frames, xy[p], cd[p], tp[p]);
+        else
+            gather_taps<false>(frames, xy[p], cd[p], tp[p]);
+    }
     uint32_t rgb[4][3];
     f32x2_t gain[4];
 #pragma unroll
@@ -1448,16 +1559,22 @@ __global__ void __launch_bounds__(256) stitch_wide_kernel(FrameSet frames, Tiled
     // camera word: camera | the half's quarters' result bits << 8 | G0 bits << 12 (tiling.cpp), i.e. the
     // item flags of a half 0
     const uint32_t fl = ((camb >> 8) & 15u) | ((camb >> 12) & 15u) << 8;
-    store_half<MODE>(of, ro, rgba.res_rgba != 0, finish_any<MODE>(rgbf, gain), camb & 31u, fl, 0, x, y, x < W && y < H);
+    store_half<MODE, kOutRuntime>(of, ro, rgba.res_rgba != 0, finish_any<MODE>(rgbf, gain), camb & 31u, fl, 0, x, y,
+                                  x < W && y < H);
 }
 
 // The weight table's address (wtab_read) assumes the dynamic LDS starts right after StitchLds: checked
 // once per kernel instance against the compiled static LDS size.
-template <bool DW, int MODE, bool V, bool TEX, int LG, bool E24>
+template <bool DW, int MODE, bool V, bool TEX, int LG, bool E24, int PF>
 static hipError_t stitch_lds_check() {
     hipFuncAttributes a;
-    const void* k = TEX ? reinterpret_cast<const void*>(stitch_tiled_tex_kernel<DW, MODE, V, LG>)
-                        : reinterpret_cast<const void*>(stitch_tiled_kernel<DW, MODE, V, LG, E24>);
+    const void* k;
+    if constexpr (PF == kPfRuntime)
+        k = reinterpret_cast<const void*>(stitch_tiled_pix_kernel<MODE, TEX, LG, E24>);
+    else if constexpr (TEX)
+        k = reinterpret_cast<const void*>(stitch_tiled_tex_kernel<DW, MODE, V, LG>);
+    else
+        k = reinterpret_cast<const void*>(stitch_tiled_kernel<DW, MODE, V, LG, E24, PF>);
     const hipError_t e = hipFuncGetAttributes(&a, k);
     if (e != hipSuccess) return e;
     return a.sharedSizeBytes == sizeof(StitchLds) ? hipSuccess : hipErrorInvalidKernelFile;
@@ -1466,21 +1583,28 @@ static hipError_t stitch_lds_check() {
 // dynamic LDS of the composite: the weight table, then the frames' camera gains (FrameBatch order)
 constexpr uint32_t kStitchDynLds = kWtabBytes + 4u * 2u * kMaxCams;
 
-template <bool DW, int MODE, bool V, bool TEX, int LG, bool E24>
+template <bool DW, int MODE, bool V, bool TEX, int LG, bool E24, int PF>
 static hipError_t launch_tiled(int blocks, const FrameBatch<1 << LG>& frames, const TiledLut& lut, int W, int H, int use_gain,
-                               int64_t out_pitch, const RgbaOut& rgba, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    static const hipError_t lds_ok = stitch_lds_check<DW, MODE, V, TEX, LG, E24>();
+                               int64_t out_pitch, const RgbaOut& rgba, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
+                               int pix) {
+    static_assert(PF != kPfNv12 || !TEX, "compiled-in NV12: the default sampling's instances");
+    static const hipError_t lds_ok = stitch_lds_check<DW, MODE, V, TEX, LG, E24, PF>();
     if (lds_ok != hipSuccess) return lds_ok;
-    if constexpr (TEX) {
+    if constexpr (PF == kPfRuntime) {
+        if (ev0) (void)hipEventRecord(ev0, s);
+        hipLaunchKernelGGL((stitch_tiled_pix_kernel<MODE, TEX, LG, E24>), dim3(blocks), dim3(256), kStitchDynLds, s,
+                           frames, lut, W, H, use_gain, out_pitch, rgba, pix);
+        if (ev0) (void)hipEventRecord(ev1, s);
+    } else if constexpr (TEX) {
         // (no packet-carried timing events: the texture convention is not a bench line's timed kernel)
         hipLaunchKernelGGL((stitch_tiled_tex_kernel<DW, MODE, V, LG>), dim3(blocks), dim3(256), kStitchDynLds, s,
                            frames, lut, W, H, use_gain, out_pitch, rgba);
         if (ev0) (void)hipEventRecord(ev1, s);
     } else if (ev0) {  // the timing events carried by the dispatch packet itself
-        hipExtLaunchKernelGGL((stitch_tiled_kernel<DW, MODE, V, LG, E24>), dim3(blocks), dim3(256), kStitchDynLds, s, ev0,
+        hipExtLaunchKernelGGL((stitch_tiled_kernel<DW, MODE, V, LG, E24, PF>), dim3(blocks), dim3(256), kStitchDynLds, s, ev0,
                               ev1, 0, frames, lut, W, H, use_gain, out_pitch, rgba);
     } else {
-        hipLaunchKernelGGL((stitch_tiled_kernel<DW, MODE, V, LG, E24>), dim3(blocks), dim3(256), kStitchDynLds, s, frames,
+        hipLaunchKernelGGL((stitch_tiled_kernel<DW, MODE, V, LG, E24, PF>), dim3(blocks), dim3(256), kStitchDynLds, s, frames,
                            lut, W, H, use_gain, out_pitch, rgba);
     }
     return hipGetLastError();
@@ -1499,34 +1623,45 @@ static void frame_batch(const FrameSet* frames, const double* const* gains, uint
     }
 }
 
-template <bool DW, int MODE, bool V, bool TEX, bool E24>
+template <bool DW, int MODE, bool V, bool TEX, bool E24, int PF = kPfPlanar>
 static hipError_t launch_tiled_lg(int lg, int blocks, const FrameSet* frames, const double* const* gains,
                                   uint8_t* const* out, const TiledLut& lut, int W, int H, int use_gain,
                                   int64_t out_pitch, const RgbaOut& rgba, hipStream_t s, hipEvent_t ev0,
-                                  hipEvent_t ev1) {
+                                  hipEvent_t ev1, int pix = 0) {
     if constexpr (MODE == 0) {
         if (lg == 1) {
             FrameBatch<2> fb;
             frame_batch<1>(frames, gains, out, fb);
-            return launch_tiled<DW, MODE, V, TEX, 1, E24>(blocks, fb, lut, W, H, use_gain, out_pitch, rgba, s, ev0, ev1);
+            return launch_tiled<DW, MODE, V, TEX, 1, E24, PF>(blocks, fb, lut, W, H, use_gain, out_pitch, rgba, s, ev0, ev1, pix);
         }
         if (lg == 2) {
             FrameBatch<4> fb;
             frame_batch<2>(frames, gains, out, fb);
-            return launch_tiled<DW, MODE, V, TEX, 2, E24>(blocks, fb, lut, W, H, use_gain, out_pitch, rgba, s, ev0, ev1);
+            return launch_tiled<DW, MODE, V, TEX, 2, E24, PF>(blocks, fb, lut, W, H, use_gain, out_pitch, rgba, s, ev0, ev1, pix);
         }
     }
     if (lg != 0) return hipErrorInvalidValue;
     FrameBatch<1> fb;
     frame_batch<0>(frames, gains, out, fb);
-    return launch_tiled<DW, MODE, V, TEX, 0, E24>(blocks, fb, lut, W, H, use_gain, out_pitch, rgba, s, ev0, ev1);
+    return launch_tiled<DW, MODE, V, TEX, 0, E24, PF>(blocks, fb, lut, W, H, use_gain, out_pitch, rgba, s, ev0, ev1, pix);
 }
 
 // the instance for the frames' staging (dword loads, vignette) and the entries' convention
 template <int MODE, bool TEX, bool E24>
 static hipError_t launch_tiled_vd(bool dw, bool vig, int lg, int blocks, const FrameSet* fr, const double* const* g,
                                   uint8_t* const* o, const TiledLut& lut, int W, int H, int use_gain, int64_t out_pitch,
-                                  const RgbaOut& rgba, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+                                  const RgbaOut& rgba, hipStream_t s, hipEvent_t e0, hipEvent_t e1, int pix) {
+    if (pix) {
+        // NV12 in and out, default sampling, aligned frames without vignette, blend 0: the compiled-in instance;
+        // every other launch with an NV12 side: the instance that takes the layouts from `pix`
+        if constexpr (MODE == 0 && !TEX) {
+            if (pix == (kPixInNv12 | kPixOutNv12) && dw && !vig)
+                return launch_tiled_lg<true, MODE, false, TEX, E24, kPfNv12>(lg, blocks, fr, g, o, lut, W, H, use_gain,
+                                                                              out_pitch, rgba, s, e0, e1, pix);
+        }
+        return launch_tiled_lg<false, MODE, true, TEX, E24, kPfRuntime>(lg, blocks, fr, g, o, lut, W, H, use_gain, out_pitch,
+                                                                        rgba, s, e0, e1, pix);
+    }
     if (dw && !vig)
         return launch_tiled_lg<true, MODE, false, TEX, E24>(lg, blocks, fr, g, o, lut, W, H, use_gain, out_pitch, rgba, s, e0, e1);
     if (dw)
@@ -1540,14 +1675,14 @@ static hipError_t launch_tiled_vd(bool dw, bool vig, int lg, int blocks, const F
 template <int MODE, bool TEX>
 static hipError_t launch_tiled_for(bool dw, bool vig, int lg, int blocks, const FrameSet* fr, const double* const* g,
                                    uint8_t* const* o, const TiledLut& lut, int W, int H, int use_gain, int64_t out_pitch,
-                                   const RgbaOut& rgba, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+                                   const RgbaOut& rgba, hipStream_t s, hipEvent_t e0, hipEvent_t e1, int pix) {
     if constexpr (!TEX) {
         if (lut.e24)
-            return launch_tiled_vd<MODE, TEX, true>(dw, vig, lg, blocks, fr, g, o, lut, W, H, use_gain, out_pitch, rgba, s, e0, e1);
+            return launch_tiled_vd<MODE, TEX, true>(dw, vig, lg, blocks, fr, g, o, lut, W, H, use_gain, out_pitch, rgba, s, e0, e1, pix);
     } else {
         if (lut.e24) return hipErrorInvalidValue;  // texture-convention entries are never packed
     }
-    return launch_tiled_vd<MODE, TEX, false>(dw, vig, lg, blocks, fr, g, o, lut, W, H, use_gain, out_pitch, rgba, s, e0, e1);
+    return launch_tiled_vd<MODE, TEX, false>(dw, vig, lg, blocks, fr, g, o, lut, W, H, use_gain, out_pitch, rgba, s, e0, e1, pix);
 }
 
 // nf frame sets (1, 2 or 4) in one launch of the tiled kernel (FrameBatch); wide tiles one launch per frame
@@ -1555,7 +1690,8 @@ template <int MODE>
 static hipError_t launch_composite(const FrameSet* frames, int nf, const TiledLut& lut, int W, int H,
                                    const double* const* gains, int use_gain, uint8_t* const* out, int64_t out_pitch,
                                    const RgbaOut& rgba, hipStream_t s, hipEvent_t ev0 = nullptr,
-                                   hipEvent_t ev1 = nullptr) {
+                                   hipEvent_t ev1 = nullptr, int pix = 0) {
+    if (pix & ~(kPixInNv12 | kPixOutNv12)) return hipErrorInvalidValue;
     if (lut.n_items > 0 && lut.qpl != kItemHalves) return hipErrorInvalidValue;
     const int lg = nf == 1 ? 0 : nf == 2 ? 1 : nf == 4 ? 2 : -1;
     if (lg < 0 || (MODE == 1 && nf != 1)) return hipErrorInvalidValue;
@@ -1591,15 +1727,15 @@ static hipError_t launch_composite(const FrameSet* frames, int nf, const TiledLu
         hipEvent_t e0 = ext_ev ? ev0 : nullptr, e1 = ext_ev ? ev1 : nullptr;
         const hipError_t e =
             lut.tex ? launch_tiled_for<MODE, true>(dw, vig, lg, blocks, frames, gains, out, lut, W, H, use_gain, out_pitch,
-                                                   rgba, s, e0, e1)
+                                                   rgba, s, e0, e1, pix)
                     : launch_tiled_for<MODE, false>(dw, vig, lg, blocks, frames, gains, out, lut, W, H, use_gain, out_pitch,
-                                                    rgba, s, e0, e1);
+                                                    rgba, s, e0, e1, pix);
         if (e != hipSuccess) return e;
     }
     if (lut.n_wide > 0)
         for (int f = 0; f < nf; f++)
             hipLaunchKernelGGL(stitch_wide_kernel<MODE>, dim3(lut.n_wide), dim3(256), 0, s, frames[f], lut, W, H,
-                               gains[f], use_gain, out ? out[f] : nullptr, out_pitch, rgba);
+                               gains[f], use_gain, out ? out[f] : nullptr, out_pitch, rgba, pix);
     if (ev0 && !ext_ev) {
         const hipError_t e = hipEventRecord(ev1, s);
         if (e != hipSuccess) return e;
@@ -1611,20 +1747,23 @@ int composite_qpl() { return kItemHalves; }
 
 hipError_t launch_stitch_batch(const FrameSet* frames, int nf, const TiledLut& lut, int W, int H,
                                const double* const* gains, int use_gain, uint8_t* const* out, int64_t out_pitch,
-                               hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+                               hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int pix) {
     if (nf < 1 || nf > kMaxBatch) return hipErrorInvalidValue;
-    return launch_composite<0>(frames, nf, lut, W, H, gains, use_gain, out, out_pitch, RgbaOut{}, s, ev0, ev1);
+    return launch_composite<0>(frames, nf, lut, W, H, gains, use_gain, out, out_pitch, RgbaOut{}, s, ev0, ev1, pix);
 }
 
 hipError_t launch_stitch(const FrameSet& frames, const TiledLut& lut, int W, int H, const double* gains,
-                         int use_gain, uint8_t* out, int64_t out_pitch, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    return launch_composite<0>(&frames, 1, lut, W, H, &gains, use_gain, &out, out_pitch, RgbaOut{}, s, ev0, ev1);
+                         int use_gain, uint8_t* out, int64_t out_pitch, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
+                         int pix) {
+    return launch_composite<0>(&frames, 1, lut, W, H, &gains, use_gain, &out, out_pitch, RgbaOut{}, s, ev0, ev1, pix);
 }
 
 hipError_t launch_mb_remap(const FrameSet& frames, const TiledLut& lut, const double* gains, int use_gain,
-                           const RgbaOut& out, hipStream_t s) {
+                           const RgbaOut& out, hipStream_t s, int pix) {
     // W, H: no level-grid bound of its own (the per-camera ROI check drops what lies outside)
-    return launch_composite<1>(&frames, 1, lut, 1 << 16, 1 << 16, &gains, use_gain, nullptr, 0, out, s);
+    // (the result frame's layout travels in `out`; a planar launch keeps the planar instances)
+    const int p = (pix & kPixInNv12) | ((out.res && !out.res_rgba && out.res_v_off == 0u) ? kPixOutNv12 : 0);
+    return launch_composite<1>(&frames, 1, lut, 1 << 16, 1 << 16, &gains, use_gain, nullptr, 0, out, s, nullptr, nullptr, p);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1804,8 +1943,8 @@ hipError_t launch_resize_u8(const uint8_t* src, int sw, int sh, int64_t spitch, 
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) resize_rgba_yuv420_kernel(const uint8_t* __restrict__ rgba, int sw, int sh,
                                                                  int64_t spitch, float fx, float fy, uint8_t* out,
-                                                                 int dw, int dh, int64_t out_pitch) {
-    const OutFrame of = make_out_frame(out, dw, dh, out_pitch);
+                                                                 int dw, int dh, int64_t out_pitch, int out_nv12) {
+    const OutFrame of = make_out_frame(out, dw, dh, out_pitch, out_nv12 != 0);
     const int qw = dw >> 1, qh = dh >> 1;
     const int64_t total = (int64_t)qw * qh;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
@@ -1836,19 +1975,19 @@ __global__ void __launch_bounds__(256) resize_rgba_yuv420_kernel(const uint8_t* 
                 rgb[p][ch] = (uint32_t)sat_u8_rne(o);
             }
         }
-        store_quad(of, finish_quad_u8(rgb), 2 * qx, 2 * qy, true);  // rgb already 0..255
+        store_quad<kOutRuntime>(of, finish_quad_u8(rgb), 2 * qx, 2 * qy, true);  // rgb already 0..255
     }
 }
 
 hipError_t launch_resize_rgba_yuv420(const uint8_t* rgba, int sw, int sh, int64_t spitch, uint8_t* out, int dw, int dh,
-                                     int64_t out_pitch, hipStream_t s) {
+                                     int64_t out_pitch, hipStream_t s, int out_nv12) {
     if (dw <= 0 || dh <= 0 || (dw & 1) || (dh & 1)) return hipErrorInvalidValue;
     // resize.cpp:82-83,105: the kernel gets (float)(1.0 / (double(dsize) / src))
     const float fx = (float)(1.0 / ((double)dw / sw)), fy = (float)(1.0 / ((double)dh / sh));
     const int64_t total = (int64_t)(dw / 2) * (dh / 2);
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 16);
     hipLaunchKernelGGL(resize_rgba_yuv420_kernel, dim3(blocks), dim3(256), 0, s, rgba, sw, sh, spitch, fx, fy, out, dw,
-                       dh, out_pitch);
+                       dh, out_pitch, out_nv12);
     return hipGetLastError();
 }
 

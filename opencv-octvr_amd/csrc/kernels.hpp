@@ -146,7 +146,12 @@ static_assert(256 + kStridePadMax < (1u << kStrideBits), "a padded stride fits i
 constexpr int kGroupFirst = 4;
 constexpr uint32_t kGroupValid = 0x8000u;
 
-// One input camera as the per-frame kernels see it: a YUV420P frame in "Y over [U|V]" layout.
+// Pixel layouts of a stitch (octvr_mapper_set_pixel_formats), a launch argument: the inputs' (all alike) and
+// the output's chroma rows hold a U half and a V half ("Y over [U|V]", the default) or, with the bit set,
+// U,V byte pairs (NV12).  The luma rows, the sizes and the pitch rules are the same.
+constexpr int kPixInNv12 = 1, kPixOutNv12 = 2;
+
+// One input camera as the per-frame kernels see it: a YUV420P frame in "Y over [U|V]" layout (or NV12, kPixInNv12).
 struct SourceFrame {
     const uint8_t* yuv;
     int32_t w, h;
@@ -234,7 +239,8 @@ hipError_t launch_composite_lut(const CamTemplate* cams_dev, int n, int W, int H
 hipError_t launch_gain_feed(const FrameSet& frames, const CompositeEntry* samples, const uint16_t* partners, int tex,
                             int n_chunks, const int32_t* N, int n,
                             unsigned long long* totals, uint32_t* tickets, double* gains, hipStream_t s,
-                            bool lean = false);  // lean: <= 80 VGPRs (73 used), runs beside a composite (kernels.hip)
+                            bool lean = false,  // lean: <= 80 VGPRs (73 used), runs beside a composite (kernels.hip)
+                            int pix = 0);       // kPixInNv12: the frames are NV12
 
 // FastMapper frames of one launch (octvr_fastmapper_stitch_nv12_batch): camera c of frame f at
 // src[(f << cam_log2) + c] (cam_log2 5 for up to 2 frames, 4 for 4), the frames' NV12 outputs.
@@ -255,7 +261,7 @@ struct FeedBatch {
 };
 hipError_t launch_gain_feed_batch(const FrameSet* frames, int nf, const CompositeEntry* samples, const uint16_t* partners,
                                   int tex, int n_chunks, const int32_t* N, int n, unsigned long long* const* totals,
-                                  uint32_t* const* tickets, double* const* gains, hipStream_t s, bool lean);
+                                  uint32_t* const* tickets, double* const* gains, hipStream_t s, bool lean, int pix = 0);
 
 hipError_t launch_set_gains(const double* host_gains, int n, double* gains_dev, hipStream_t s);
 
@@ -330,15 +336,15 @@ __host__ __device__ constexpr uint32_t tiled_entry_tex(uint32_t off, uint32_t ab
 int composite_qpl();
 
 // ev0 / ev1 (optional): timing events around the composite (carried by the dispatch packet when it
-// is a single launch)
+// is a single launch).  pix: the layouts of the frames and of `out` (kPixInNv12 | kPixOutNv12)
 hipError_t launch_stitch(const FrameSet& frames_dev, const TiledLut& lut, int W, int H,
                          const double* gains, int use_gain, uint8_t* out, int64_t out_pitch, hipStream_t s,
-                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int pix = 0);
 // nf frames (1, 2 or 4; frame f = frames[f], gains[f], out[f], all outputs of pitch out_pitch) in one
 // composite launch (FrameBatch); more than 16 cameras need nf <= 2
 hipError_t launch_stitch_batch(const FrameSet* frames, int nf, const TiledLut& lut, int W, int H,
                                const double* const* gains, int use_gain, uint8_t* const* out, int64_t out_pitch,
-                               hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+                               hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int pix = 0);
 
 // ---- multi-band blend (blend > 0): MultiBandGPUBlender (blenders.cpp:589-735) ------------------
 // Level l of the blend lives on the "level grid": align_result_roi >> l.  Each camera keeps its
@@ -426,7 +432,8 @@ struct RgbaOut {
     // so the level-0 blend skips those tiles; items flagged kItemNoG0 write no G0 for that half (nothing
     // reads it).  The result frame is addressed from the level-0 grid origin (align_result_roi's
     // top-left): `res` points there, YUV420P with the U / V planes at res_u_off / res_v_off bytes
-    // (res_rgba = 0), or the RGBA result image of a scaled output (res_rgba = 1).  Flagged tiles lie
+    // (res_rgba = 0; an NV12 frame: its U,V pairs at res_u_off, res_v_off = 0, as OutFrame), or the RGBA
+    // result image of a scaled output (res_rgba = 1).  Flagged tiles lie
     // wholly inside the crop and the frame (multiband_create), so the stores need no bounds.
     uint8_t* res;
     uint32_t res_bytes;    // addressable bytes from `res` (< 2^31)
@@ -446,7 +453,8 @@ __host__ __device__ constexpr uint32_t item_g0_bit(int h, int q) { return 1u << 
 constexpr uint32_t kItemAllG0 = 0xFF00u;
 
 hipError_t launch_mb_remap(const FrameSet& frames, const TiledLut& lut, const double* gains, int use_gain,
-                           const RgbaOut& out, hipStream_t s);
+                           const RgbaOut& out, hipStream_t s, int pix = 0);  // pix: kPixInNv12 (the result frame's
+                                                                             // layout travels in RgbaOut)
 // fastPyrDown<uchar4> (fast_pyr_down.cu:17-76) of every listed (camera, tile) of level l from l - 1.
 hipError_t launch_mb_down(const uint2* items, int n_items, const MbCamLevel* cams_l, const MbCamLevel* cams_prev,
                           const uint8_t* g_prev, uint8_t* g_l, hipStream_t s);
@@ -474,8 +482,9 @@ struct MbBlendArgs {
     const int32_t* rup_r0;          // per tile row / column: origin of the staged collapse patch
     const int32_t* rup_c0;
     int16_t* r_out;                 // level > 0: collapsed level (s16x4, pitch 4 * W shorts)
-    uint8_t* out;                   // level 0: YUV420P output frame
+    uint8_t* out;                   // level 0: YUV420P output frame (out_nv12: NV12)
     int64_t out_pitch;
+    int out_nv12;
     int out_w, out_h;
     int ax, ay, crop_w, crop_h;     // align_result_roi origin in the output frame, crop size
     uint8_t* rgba;                  // level 0, scaled output: the RGB result as RGBA (out_w x out_h) instead of YUV
@@ -519,7 +528,7 @@ hipError_t launch_resize_u8(const uint8_t* src, int sw, int sh, int64_t spitch, 
 // Scaled output (mapper.cpp:290-306): cuda::resize INTER_LINEAR of the RGB(A) result (sw x sh,
 // pitch spitch bytes, 4 bytes per pixel) to dw x dh (even), then RGB -> YUV420P into `out`.
 hipError_t launch_resize_rgba_yuv420(const uint8_t* rgba, int sw, int sh, int64_t spitch, uint8_t* out, int dw, int dh,
-                                     int64_t out_pitch, hipStream_t s);
+                                     int64_t out_pitch, hipStream_t s, int out_nv12 = 0);
 
 // Preview output (mapper.cpp:308-312): cuda::resize INTER_LINEAR of the RGB(A) result to a dw x dh
 // CV_8UC3 image (3 bytes per pixel, pitch out_pitch).

@@ -518,8 +518,8 @@ __global__ void __launch_bounds__(256, kBlendWaves) mb_blend_kernel(MbBlendArgs 
         }
         return;
     }
-    const OutFrame of = make_out_frame(a.out, a.out_w, a.out_h, a.out_pitch);
-    store_quad(of, finish_quad_u8(rgb), ox, oy, in);  // rgb already 0..255
+    const OutFrame of = make_out_frame(a.out, a.out_w, a.out_h, a.out_pitch, a.out_nv12 != 0);
+    store_quad<kOutRuntime>(of, finish_quad_u8(rgb), ox, oy, in);  // rgb already 0..255
 }
 
 hipError_t launch_mb_blend(const MbBlendArgs& a, hipStream_t s) {

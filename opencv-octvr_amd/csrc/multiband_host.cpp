@@ -855,7 +855,8 @@ void multiband_set_slots(MultiBand& M, int k) {
 }
 
 void multiband_run(MultiBand& M, int slot, const FrameSet& frames, const double* gains_dev, int use_gain, uint8_t* out,
-                   int64_t out_pitch, hipStream_t s, uint8_t* rgba, int64_t rgba_pitch) {
+                   int64_t out_pitch, hipStream_t s, uint8_t* rgba, int64_t rgba_pitch, int pix) {
+    const bool out_nv12 = !rgba && (pix & kPixOutNv12);
     REQUIRE(slot >= 0 && slot <= (int)M.extra.size(), "bad frame slot");
     MultiBand::FrameBufs* fb = slot ? M.extra[slot - 1].get() : nullptr;
     auto G = [&](int l) { return fb ? fb->g[l].p : M.lv[l].g.p; };
@@ -889,15 +890,17 @@ void multiband_run(MultiBand& M, int slot, const FrameSet& frames, const double*
             const int64_t o = (int64_t)M.arr.y * out_pitch + M.arr.x;
             const int64_t total = out_pitch * (M.out_h + M.out_h / 2);
             REQUIRE(total < ((int64_t)1 << 31) - 64, "output frame exceeds 2 GiB");
-            const int64_t u = (int64_t)M.out_h * out_pitch + (int64_t)(M.arr.y / 2) * out_pitch + M.arr.x / 2;
+            // (NV12: the U,V pair of luma column x at chroma byte x & ~1, and res_v_off = 0 says so)
+            const int64_t u = (int64_t)M.out_h * out_pitch + (int64_t)(M.arr.y / 2) * out_pitch +
+                              (out_nv12 ? (M.arr.x & ~1) : M.arr.x / 2);
             ro.res = out + o;
             ro.res_bytes = (uint32_t)(total - o);
             ro.res_pitch = (uint32_t)out_pitch;
             ro.res_u_off = (uint32_t)(u - o);
-            ro.res_v_off = (uint32_t)(u - o + M.out_w / 2);
+            ro.res_v_off = out_nv12 ? 0u : (uint32_t)(u - o + M.out_w / 2);
         }
     }
-    HIP_CHECK(launch_mb_remap(frames, view, gains_dev, use_gain, ro, s));
+    HIP_CHECK(launch_mb_remap(frames, view, gains_dev, use_gain, ro, s, pix));
     for (int l = 1; l <= M.B; l++) {
         auto& L = M.lv[l];
         HIP_CHECK(launch_mb_down(L.down_items.p, L.n_down, L.cams.p, M.lv[l - 1].cams.p, G(l - 1), G(l), s));
@@ -937,6 +940,7 @@ void multiband_run(MultiBand& M, int slot, const FrameSet& frames, const double*
         } else {
             a.out = out;
             a.out_pitch = out_pitch;
+            a.out_nv12 = out_nv12 ? 1 : 0;
             a.out_w = M.out_w;
             a.out_h = M.out_h;
             a.ax = M.arr.x;

@@ -906,6 +906,7 @@ struct octvr_mapper {
     int cur_slot = 0;                                  // slot of the last stitch
     int timing = 0;             // event-timing period in stitches (0 = off)
     uint64_t timed_calls = 0;
+    int pix = 0;                // layouts of the inputs and the output (octvr_mapper_set_pixel_formats): kPixInNv12 | kPixOutNv12
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events, free_events;  // recorded / reusable
     ~octvr_mapper() {
         for (auto& sl : slots)
@@ -1161,7 +1162,7 @@ void stitch_gains(octvr_mapper* m, octvr_mapper::FrameSlot& sl, const FrameSet& 
         // variant fits next to it (the wide-prefetch one waits for its workgroups to drain)
         const bool lean = m->slots.size() > 1;
         HIP_CHECK(launch_gain_feed(fs, m->samples.p, m->partners.p, m->tex, m->n_chunks, m->N.p, m->n, sl.totals,
-                                   sl.tickets, sl.gains, s, lean));
+                                   sl.tickets, sl.gains, s, lean, m->pix));
     }
 }
 
@@ -1216,21 +1217,22 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
             // stitch at template size into the RGB(A) result, then resize + RGB -> YUV420P (mapper.cpp:290-306)
             // (one frame slot only: the result frame is shared); without scaling the resize is the identity
             if (m->mb)
-                multiband_run(*m->mb, 0, fs, sl.gains, m->use_gain, nullptr, 0, s, m->result.p, (int64_t)m->W * 4);
+                multiband_run(*m->mb, 0, fs, sl.gains, m->use_gain, nullptr, 0, s, m->result.p, (int64_t)m->W * 4, m->pix);
             else
                 HIP_CHECK(launch_mb_remap(fs, m->tiles.view, sl.gains, m->use_gain,
-                                          RgbaOut{m->result.p, (uint32_t)m->result.n, m->result_view.p}, s));
+                                          RgbaOut{m->result.p, (uint32_t)m->result.n, m->result_view.p}, s, m->pix));
             HIP_CHECK(launch_resize_rgba_yuv420(m->result.p, m->W, m->H, (int64_t)m->W * 4, out_dev, m->SW, m->SH,
-                                                (int64_t)out_pitch, s));
+                                                (int64_t)out_pitch, s, (m->pix & kPixOutNv12) != 0));
             if (preview)  // cuda::resize(result, preview_output, ...) (mapper.cpp:308-312)
                 HIP_CHECK(launch_resize_rgba_rgb(m->result.p, m->W, m->H, (int64_t)m->W * 4, preview->dev, preview->w,
                                                  preview->h, (int64_t)preview->pitch, s));
         } else if (m->mb) {
-            multiband_run(*m->mb, k, fs, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s);
+            multiband_run(*m->mb, k, fs, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s, nullptr, 0, m->pix);
         } else {
             TiledLut view = m->tiles.view;
             view.queue = sl.queue;
-            HIP_CHECK(launch_stitch(fs, view, m->W, m->H, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s, e0, e1));
+            HIP_CHECK(launch_stitch(fs, view, m->W, m->H, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s, e0, e1,
+                                    m->pix));
         }
         if (timed) {
             if (m->scaled || m->mb || preview) HIP_CHECK(hipEventRecord(e1, s));
@@ -1283,12 +1285,12 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
     }
     if (feed)  // GainCompensatorGPU::feed of each frame (exposure_compensate.cpp:223-297), all in one launch
         HIP_CHECK(launch_gain_feed_batch(fs, nb, m->samples.p, m->partners.p, m->tex, m->n_chunks, m->N.p, m->n, tot, tick,
-                                         gd, s, true));
+                                         gd, s, true, m->pix));
     const auto ev = stitch_events(m);
     TiledLut view = m->tiles.view;
     view.queue = m->slots[ks[0]].queue;  // this launch's work counters (the first frame's slot)
     HIP_CHECK(launch_stitch_batch(fs, nb, view, m->W, m->H, g, m->use_gain, out_dev, (int64_t)out_pitch, s, ev.first,
-                                  ev.second));
+                                  ev.second, m->pix));
     if (ev.first) m->events.emplace_back(ev.first, ev.second);
     for (int f = 0; f < nb; f++) {
         octvr_mapper::FrameSlot& sl = m->slots[ks[f]];
@@ -1816,6 +1818,27 @@ int octvr_mapper_set_frames_in_flight(octvr_mapper* m, int k) {
         }
         if (m->mb) multiband_set_slots(*m->mb, k);
         HIP_CHECK(hipDeviceSynchronize());  // the memsets complete before any stream uses the slots
+    });
+}
+
+int octvr_mapper_set_pixel_formats(octvr_mapper* m, int in_format, int out_format) {
+    return guarded([&] {
+        REQUIRE(m, "NULL argument");
+        REQUIRE((in_format == OCTVR_PIX_YUV420P || in_format == OCTVR_PIX_NV12) &&
+                    (out_format == OCTVR_PIX_YUV420P || out_format == OCTVR_PIX_NV12),
+                "pixel format must be OCTVR_PIX_YUV420P or OCTVR_PIX_NV12");
+        DeviceGuard dg(m->device);
+        for (auto& sl : m->slots)  // stitches in flight keep the layouts they were issued with
+            if (sl.done) HIP_CHECK(hipEventSynchronize(sl.done));
+        m->pix = (in_format == OCTVR_PIX_NV12 ? kPixInNv12 : 0) | (out_format == OCTVR_PIX_NV12 ? kPixOutNv12 : 0);
+    });
+}
+
+int octvr_mapper_pixel_formats(const octvr_mapper* m, int* in_format, int* out_format) {
+    return guarded([&] {
+        REQUIRE(m && in_format && out_format, "NULL argument");
+        *in_format = (m->pix & kPixInNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
+        *out_format = (m->pix & kPixOutNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
     });
 }
 

@@ -79,6 +79,9 @@ _lib.octvr_mapper_stitch_preview.argtypes = [_VP, C.POINTER(_VP), C.POINTER(C.c_
                                              C.c_int, C.c_size_t, C.POINTER(C.c_double), C.c_int, _VP]
 _lib.octvr_mapper_gains.argtypes = [_VP, C.POINTER(C.c_double), C.c_int]
 _lib.octvr_mapper_set_frames_in_flight.argtypes = [_VP, C.c_int]
+if hasattr(_lib, "octvr_mapper_set_pixel_formats"):  # (absent from libraries built before NV12: scripts/ab.sh variants)
+    _lib.octvr_mapper_set_pixel_formats.argtypes = [_VP, C.c_int, C.c_int]
+    _lib.octvr_mapper_pixel_formats.argtypes = [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 _lib.octvr_mapper_traffic.argtypes = [_VP, C.POINTER(C.c_double)]
 _lib.octvr_mapper_set_timing.argtypes = [_VP, C.c_int]
 _lib.octvr_mapper_kernel_time.argtypes = [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -404,6 +407,48 @@ class BatchRefs:
         assert all(o.stride(0) == self.out_pitch for o in outputs), "the outputs of a batch share one pitch"
 
 
+PIX_YUV420P, PIX_NV12 = 0, 1  # OCTVR_PIX_*
+PIX_NAMES = ("yuv420p", "nv12")
+
+
+def _pix_value(fmt):
+    if isinstance(fmt, str):
+        if fmt.lower() not in PIX_NAMES:
+            raise ValueError("pixel format must be 'yuv420p' or 'nv12'")
+        return PIX_NAMES.index(fmt.lower())
+    return int(fmt)  # the library rejects unknown values (OCTVR_E_INVALID)
+
+
+def _chroma_frame(frame, w, h):
+    f = np.asarray(frame)
+    w, h = int(w), int(h)
+    if w <= 0 or h <= 0 or (w & 1) or (h & 1):
+        raise ValueError("4:2:0 frames have even width and height")
+    if f.ndim != 2 or f.dtype != np.uint8 or f.shape[0] != h * 3 // 2 or f.shape[1] < w:
+        raise ValueError("expected a uint8 frame of 3h/2 rows and at least w columns")
+    return f, w, h
+
+
+def nv12_from_yuv420p(frame, w, h):
+    """The NV12 frame (h rows of Y, then h/2 rows of U,V byte pairs) of a "Y over [U|V]" frame (h rows of Y,
+    then h/2 rows with U in bytes [0, w/2) and V in [w/2, w)): a new 3h/2 x w array.  Columns of `frame` past
+    w (a pitch) are dropped."""
+    f, w, h = _chroma_frame(frame, w, h)
+    out = np.array(f[:, :w], dtype=np.uint8, order="C")
+    out[h:, 0::2] = f[h:, :w // 2]
+    out[h:, 1::2] = f[h:, w // 2:w]
+    return out
+
+
+def yuv420p_from_nv12(frame, w, h):
+    """The inverse of nv12_from_yuv420p."""
+    f, w, h = _chroma_frame(frame, w, h)
+    out = np.array(f[:, :w], dtype=np.uint8, order="C")
+    out[h:, :w // 2] = f[h:, 0:w:2]
+    out[h:, w // 2:] = f[h:, 1:w:2]
+    return out
+
+
 class Mapper:
     """vr::Mapper on one device: stitch(inputs YUV420P, output YUV420P) with optional gain."""
 
@@ -487,6 +532,19 @@ class Mapper:
         (octvr_mapper_set_frames_in_flight).  No scaled output; multi-band / feather mappers get
         per-slot pyramids."""
         _check(_lib.octvr_mapper_set_frames_in_flight(self._h, int(k)))
+
+    def set_pixel_formats(self, in_format="yuv420p", out_format="yuv420p"):
+        """Layouts of the input frames (all alike) and of the output of every later stitch / stitch_batch:
+        "yuv420p" ("Y over [U|V]", the default) or "nv12" (chroma rows of U,V byte pairs), or the
+        OCTVR_PIX_* values (octvr_mapper_set_pixel_formats).  Synchronizes."""
+        _check(_lib.octvr_mapper_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
+
+    @property
+    def pixel_formats(self):
+        """(input layout, output layout) as "yuv420p" / "nv12"."""
+        a, b = C.c_int(), C.c_int()
+        _check(_lib.octvr_mapper_pixel_formats(self._h, C.byref(a), C.byref(b)))
+        return PIX_NAMES[a.value], PIX_NAMES[b.value]
 
     def traffic_bytes(self):
         b = C.c_double()
