@@ -1,5 +1,6 @@
 // device_common.hpp — device-side pixel arithmetic and I/O helpers shared by the gfx950 kernels
-// (kernels.hip: remap / gain / composite; multiband.hip: pyramid blend).  Internal header.
+// (lut_kernels.hip, gain_feed.hip, composite*.hip, resize_kernels.hip: remap / gain / composite;
+// multiband.hip: pyramid blend).  Internal header.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -162,6 +163,8 @@ typedef __attribute__((address_space(1))) uint8_t gu8;
 typedef __attribute__((address_space(1))) uint16_t gu16;
 typedef __attribute__((address_space(1))) uint32_t gu32;
 typedef __attribute__((address_space(1))) uint64_t gu64;
+// a SourceFrame in the kernarg segment (constant address space): the feed's and the composite's frame tables
+typedef __attribute__((address_space(4))) const SourceFrame kSourceFrame;
 
 // wave-uniform value -> SGPR (scalar loads / branches downstream)
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }

@@ -232,14 +232,14 @@ hipError_t launch_composite_lut(const CamTemplate* cams_dev, int n, int W, int H
 
 // Gain feed in ONE launch (no host sync): each workgroup gathers its chunk's warped samples, takes
 // the f32 RGB norm (elementNorm) and adds it per partner camera into exact u64 fixed-point totals
-// (units of 2^-23, see kernels.hip); the last workgroup (per-XCD then global ticket) reads and
+// (units of 2^-23, see gain_feed.hip); the last workgroup (per-XCD then global ticket) reads and
 // resets the totals, assembles I(i,j), A, b and solves.  `totals` (kGainMaxCams^2) and `tickets`
 // (9) must be zero before the first launch; the last workgroup leaves them zero.  tex: the samples are
 // texture-convention entries (make_entry_tex).
 hipError_t launch_gain_feed(const FrameSet& frames, const CompositeEntry* samples, const uint16_t* partners, int tex,
                             int n_chunks, const int32_t* N, int n,
                             unsigned long long* totals, uint32_t* tickets, double* gains, hipStream_t s,
-                            bool lean = false,  // lean: <= 80 VGPRs (73 used), runs beside a composite (kernels.hip)
+                            bool lean = false,  // lean: <= 80 VGPRs (73 used), runs beside a composite (gain_feed.hip)
                             int pix = 0);       // kPixInNv12: the frames are NV12
 
 // FastMapper frames of one launch (octvr_fastmapper_stitch_nv12_batch): camera c of frame f at

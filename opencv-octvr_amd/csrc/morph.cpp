@@ -7,7 +7,7 @@
 //
 // Host side (this file): control-point projection, chamfer distances, the Delaunay triangulation
 // (cv::Subdiv2D restated), per-triangle affine matrices (cv::getAffineTransform + cv::solve LU) and
-// the fillPoly'd triangle ownership of every ROI pixel.  Device side (kernels.hip,
+// the fillPoly'd triangle ownership of every ROI pixel.  Device side (resize_kernels.hip,
 // morph_warp_kernel): the cv::warpAffine bilinear resampling of the three LUT planes, one pass over
 // the ROI instead of the reference's three full-ROI warps per triangle.
 #include <algorithm>

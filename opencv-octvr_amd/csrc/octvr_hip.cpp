@@ -1,6 +1,6 @@
 // octvr_hip.cpp — C ABI (include/octvr_hip.h): rig (vr::MapperTemplate) and mapper (vr::Mapper).
 //
-// Host orchestration only; all per-pixel work runs in kernels.hip.  Exceptions never cross the
+// Host orchestration only; all per-pixel work runs in the *.hip kernel files.  Exceptions never cross the
 // boundary: every entry point converts them into a status code + octvr_last_error().
 #include "octvr_hip.h"
 
@@ -1069,7 +1069,7 @@ GainPlan plan_gain(const octvr_rig& rig, int n, const std::vector<int>& in_w, co
         pmask.push_back(0);
     }
     n_chunks = (int)(uniq.size() / kGainChunk);
-    // exactness bound of the fixed-point totals (kernels.hip, gain feed): < 2^21 samples per camera
+    // exactness bound of the fixed-point totals (gain_feed.hip): < 2^21 samples per camera
     for (int i = 0; i < n; i++) REQUIRE(samp[i].size() < (1u << 21), "working-scale ROI too large for exact gain sums");
     GainPlan g;
     g.samples = std::move(uniq);
@@ -1132,12 +1132,12 @@ FrameSet frame_set(const octvr_mapper* m, const uint8_t* const* in_dev, const si
     memset(&fs, 0, sizeof fs);
     for (int i = 0; i < m->n; i++) {
         REQUIRE(in_dev[i] && in_pitch[i] >= (size_t)m->in_w[i], "bad input frame");
-        // the staging loads form row offsets with 24-bit multiplies (kernels.hip stage_load)
+        // the staging loads form row offsets with 24-bit multiplies (composite.hip stage_load)
         REQUIRE(in_pitch[i] < ((size_t)1 << 24), "input pitch must be below 16 MiB");
         // the gain feed reads frames through 32-bit buffer resources
         REQUIRE((uint64_t)in_pitch[i] * (uint64_t)(m->in_h[i] + m->in_h[i] / 2) < 0x7FFFFFFFull,
                 "input frame larger than 2 GiB");
-        // ... in 8-byte segments (kernels.hip feed_rows)
+        // ... in 8-byte segments (gain_feed.hip feed_taps_issue)
         REQUIRE((uint64_t)in_pitch[i] * (uint64_t)(m->in_h[i] + m->in_h[i] / 2) >= 8, "input frame below 8 bytes");
         fs.f[i] = SourceFrame{in_dev[i], m->in_w[i], m->in_h[i], (int64_t)in_pitch[i], m->vig[i].p};
     }

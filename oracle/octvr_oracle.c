@@ -880,7 +880,7 @@ static inline uint8_t sat_u8_rne(float v) {
 }
 
 /* The library's own BT.601 colour definitions (they stand in for NPP's closed arithmetic; parity
- * with NPP is unpinned).  Fused multiply-adds, round half to even, saturate — kernels.hip uses the
+ * with NPP is unpinned).  Fused multiply-adds, round half to even, saturate — composite.hip uses the
  * identical operation sequence. */
 static inline void yuv_px_to_rgb(int y, int u, int v, uint8_t* o) {
     float Yf = (float)y, Uf = (float)u - 128.f, Vf = (float)v - 128.f;

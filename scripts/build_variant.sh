@@ -9,10 +9,12 @@ B=/tmp/octvr_variant_$NAME; mkdir -p $B "$ROOT/opencv-octvr_amd/lib/variants"
 SRC=${SRC:-$ROOT}
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I$SRC/include -I$SRC/opencv-octvr_amd/csrc $*"
 OBJS=
-for f in octvr_hip.cpp async.cpp fastmapper.cpp seams.cpp tiling.cpp multiband_host.cpp masks.cpp morph.cpp kernels.hip multiband.hip fastmapper.hip; do
+# every source of the checkout being built (its csrc holds the library's translation units and nothing else)
+for p in "$SRC"/opencv-octvr_amd/csrc/*.cpp "$SRC"/opencv-octvr_amd/csrc/*.hip; do
+  f=${p##*/}
   o=$B/${f%.*}_${f##*.}.o
   X=; [[ $f == *.hip ]] && X="-x hip"
-  /opt/rocm/bin/hipcc $FLAGS $X -c "$SRC/opencv-octvr_amd/csrc/$f" -o $o &
+  /opt/rocm/bin/hipcc $FLAGS $X -c "$p" -o $o &
   OBJS="$OBJS $o"
 done
 wait
