@@ -38,7 +38,8 @@
 #include <thread>
 #include <vector>
 
-#include "host_common.hpp"
+#include "abi_guard.hpp"
+#include "mapper.hpp"
 
 using namespace octvr;
 
@@ -508,7 +509,7 @@ int octvr_async_create_preview(const octvr_rig* const* rigs, int n_rigs, int dev
                                const int* in_h, int out_w, int out_h, const int* blend_modes, const int* gain_modes,
                                const double* output_regions, int flags, int preview_w, int preview_h,
                                octvr_async** out) {
-    try {
+    return guarded([&] {
         REQUIRE(rigs && n_rigs > 0 && in_w && in_h && blend_modes && gain_modes && output_regions && out,
                 "NULL argument");
         REQUIRE(n_inputs > 0 && n_inputs <= kMaxCams && out_w > 0 && out_h > 0 && out_w % 2 == 0 && out_h % 2 == 0, "bad sizes");
@@ -595,14 +596,7 @@ int octvr_async_create_preview(const octvr_rig* const* rigs, int n_rigs, int dev
         for (int s = 0; s < kSlots; s++) a->free_slots.push(s);
         a->start();
         *out = a.release();
-        return OCTVR_OK;
-    } catch (const OctvrError& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return OCTVR_E_HIP;
-    }
+    }, OCTVR_E_HIP);
 }
 
 int octvr_async_push(octvr_async* a, const uint8_t* const* in_planes, const size_t* in_pitches,
@@ -674,7 +668,7 @@ int octvr_async_register_output(octvr_async* a, uint8_t* const* planes, const si
         if (r.p[0] == planes[0] && r.p[1] == planes[1] && r.p[2] == planes[2] && r.pitch[0] == pitches[0] &&
             r.pitch[1] == pitches[1] && r.pitch[2] == pitches[2])
             return OCTVR_OK;  // already registered
-    try {
+    return guarded([&] {
         DeviceGuard dg(a->device);
         octvr_async::RegOut r{};
         int done = 0;
@@ -685,18 +679,13 @@ int octvr_async_register_output(octvr_async* a, uint8_t* const* planes, const si
             if (e != hipSuccess) {
                 for (int k = 0; k < done; k++) (void)hipHostUnregister(planes[k]);
                 (void)hipGetLastError();
-                set_last_error(std::string("hipHostRegister: ") + hipGetErrorString(e));
-                return OCTVR_E_HIP;
+                throw OctvrError(OCTVR_E_HIP, std::string("hipHostRegister: ") + hipGetErrorString(e));
             }
             r.p[done] = planes[done];
             r.pitch[done] = pitches[done];
         }
         a->reg_out.push_back(r);
-        return OCTVR_OK;
-    } catch (const OctvrError& e) {
-        set_last_error(e.what());
-        return e.code;
-    }
+    }, OCTVR_E_HIP);
 }
 
 int octvr_async_unregister_output(octvr_async* a, uint8_t* const* planes) {

@@ -19,7 +19,7 @@
 #include <thread>
 #include <vector>
 
-#include "host_common.hpp"
+#include "abi_guard.hpp"
 
 using namespace octvr;
 
@@ -449,11 +449,11 @@ extern "C" {
 
 int octvr_debug_fastmapper_audit(const octvr_rig* rig, int n_inputs, const int* in_w, const int* in_h, int force_wide,
                                  int pitch_pad, char* json, size_t len) {
-    try {
+    uint64_t viol = 0;
+    const int rc = guarded([&] {
         REQUIRE(json && len > 0 && pitch_pad >= 0 && pitch_pad < 4096, "bad arguments");
         const FastPlan P = fast_plan(rig, n_inputs, in_w, in_h, force_wide != 0);
         std::string js = "{";
-        uint64_t viol = 0;
         for (int plane = 0; plane < 2; plane++) {
             const FastPlaneHost& pl = plane ? P.uv : P.y;
             AuditCounts c;
@@ -473,19 +473,13 @@ int octvr_debug_fastmapper_audit(const octvr_rig* rig, int n_inputs, const int* 
         js += "}";
         REQUIRE(js.size() < len, "buffer too small");
         memcpy(json, js.c_str(), js.size() + 1);
-        return viol ? OCTVR_E_INVALID : OCTVR_OK;
-    } catch (const OctvrError& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return OCTVR_E_INVALID;
-    }
+    }, OCTVR_E_INVALID);
+    return rc != OCTVR_OK ? rc : viol ? OCTVR_E_INVALID : OCTVR_OK;
 }
 
 int octvr_fastmapper_create(const octvr_rig* rig, int device, int n_inputs, const int* in_w, const int* in_h,
                             octvr_fastmapper** out) {
-    try {
+    return guarded([&] {
         REQUIRE(rig && in_w && in_h && out, "NULL argument");
         FastPlan P = fast_plan(rig, n_inputs, in_w, in_h, force_wide_env());
         auto fm = std::make_unique<octvr_fastmapper>();
@@ -514,19 +508,12 @@ int octvr_fastmapper_create(const octvr_rig* rig, int device, int n_inputs, cons
         upload(fm->y, P.y);
         upload(fm->uv, P.uv);
         *out = fm.release();
-        return OCTVR_OK;
-    } catch (const OctvrError& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return OCTVR_E_HIP;
-    }
+    }, OCTVR_E_HIP);
 }
 
 int octvr_fastmapper_stitch_nv12_batch(octvr_fastmapper* fm, int n_frames, const uint8_t* const* in_dev,
                                        const size_t* in_pitch, uint8_t* const* out_dev, size_t out_pitch, void* stream) {
-    try {
+    return guarded([&] {
         REQUIRE(fm && in_dev && in_pitch && out_dev, "NULL argument");
         REQUIRE(n_frames == 1 || n_frames == 2 || n_frames == 4, "a batch holds 1, 2 or 4 frames");
         REQUIRE(n_frames <= 2 || fm->n <= 16, "a batch of 4 frames holds 16 cameras per frame");
@@ -536,23 +523,13 @@ int octvr_fastmapper_stitch_nv12_batch(octvr_fastmapper* fm, int n_frames, const
         for (int f = 0; f < n_frames; f++) {
             REQUIRE(out_dev[f], "NULL output");
             memset(&fs[f], 0, sizeof fs[f]);
-            for (int i = 0; i < fm->n; i++) {
-                const uint8_t* p = in_dev[(size_t)f * fm->n + i];
-                const size_t pitch = in_pitch[(size_t)f * fm->n + i];
-                REQUIRE(p && pitch >= (size_t)fm->in_w[i] && pitch < ((size_t)1 << 24), "bad input frame");
-                REQUIRE(pitch * (size_t)(fm->in_h[i] + fm->in_h[i] / 2) >= 8 &&
-                            pitch * (size_t)(fm->in_h[i] + fm->in_h[i] / 2) < 0x7FFFFFFFull,
-                        "input frame of fewer than 8 or more than 2^31 bytes");
-                fs[f].f[i] = SourceFrame{p, fm->in_w[i], fm->in_h[i], (int64_t)pitch, nullptr};
-            }
+            for (int i = 0; i < fm->n; i++)
+                fs[f].f[i] = checked_source_frame(in_dev[(size_t)f * fm->n + i], in_pitch[(size_t)f * fm->n + i],
+                                                  fm->in_w[i], fm->in_h[i], nullptr);
         }
         HIP_CHECK(launch_fastmapper_nv12_batch(fs, n_frames, fm->y.view(), fm->uv.view(), fm->W, fm->H, out_dev,
                                                (int64_t)out_pitch, (hipStream_t)stream));
-        return OCTVR_OK;
-    } catch (const OctvrError& e) {
-        set_last_error(e.what());
-        return e.code;
-    }
+    }, OCTVR_E_HIP);
 }
 
 int octvr_fastmapper_stitch_nv12(octvr_fastmapper* fm, const uint8_t* const* in_dev, const size_t* in_pitch,

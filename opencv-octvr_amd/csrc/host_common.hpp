@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <exception>
 #include <functional>
+#include <iosfwd>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -73,9 +74,6 @@ void parallel_for(size_t n, F f) {
         for (size_t k = n * t / T; k < n * (t + 1) / T; k++) f(k);
     });
 }
-
-// octvr_last_error() text of the calling thread (octvr_hip.cpp).
-void set_last_error(const std::string& msg);
 
 // Scoped device selection: restores the caller's current device.
 struct DeviceGuard {
@@ -158,20 +156,22 @@ int rig_morph_controlpoints(octvr_rig& rig, const JsonValue& control_points);
 // cv::distanceTransform(src, dst, DIST_L2, 3) on the host (distransform.cpp:48-139); w x h, packed
 void chamfer_l2_3x3(const uint8_t* src, int w, int h, float* dist);
 
-// ---- mapper internals used by the AsyncMultiMapper pipeline (octvr_hip.cpp, async.cpp) -----------
-// preview_output of Mapper::stitch (mapper.cpp:308-312): a CV_8UC3 device image
-struct PreviewOut {
-    uint8_t* dev;
-    int w, h;
-    size_t pitch;
-};
-void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch, uint8_t* out_dev,
-                   size_t out_pitch, const double* gains, int n_gains, const double* gains_dev, hipStream_t s,
-                   const PreviewOut* preview = nullptr);
-int mapper_num_inputs(const octvr_mapper* m);
-bool mapper_has_gain(const octvr_mapper* m);
-const double* mapper_gains_dev(const octvr_mapper* m);
-void mapper_out_size(const octvr_mapper* m, int* w, int* h);
+// ---- the rig from JSON camera models (rig_json.cpp) -----------------------------------------------
+CameraParams camera_from_json(const JsonValue& cam);
+void build_camera_masks(const JsonValue& options, std::vector<uint8_t>& excl, std::vector<uint8_t>& incl);
+std::unique_ptr<octvr_rig> rig_new(const JsonValue& out_cam, int out_w, int out_h, int device);
+void rig_add(octvr_rig& rig, const JsonValue& cam, bool overlay, bool use_roi);
+JsonValue camera_json(const char* type, const char* opts_json, int flags);
+
+// ---- the rig's VRv11 .dat form, over a stream or the C ABI's callbacks (rig_dat.cpp) ---------------
+void dat_write(octvr_rig& rig, std::ostream& os);
+void dat_write(octvr_rig& rig, octvr_write_fn write, void* ctx);
+std::unique_ptr<octvr_rig> dat_read(std::istream& is);
+std::unique_ptr<octvr_rig> dat_read(octvr_read_fn read, void* ctx);
+
+// ---- one input frame as the kernels see it, with the limits of their address arithmetic checked:
+// pitch >= w and < 2^24, 8 <= bytes < 2^31 (mapper.cpp) ---------------------------------------------
+SourceFrame checked_source_frame(const uint8_t* ptr, size_t pitch, int w, int h, const float* vig);
 
 // ---- tiled composite LUT builder (tiling.cpp) ----------------------------------------------------
 struct TileJob {
@@ -242,7 +242,6 @@ struct SourceFootprint {
     double bytes() const;  // YUV420P bytes under the set bits
 };
 void footprint_add_tiles(SourceFootprint& f, const TiledLutBuild& b);
-const SourceFootprint& mapper_footprint(const octvr_mapper* m);
 
 // ---- multi-band blend (multiband_host.cpp) ---------------------------------------------------------
 class MultiBand;

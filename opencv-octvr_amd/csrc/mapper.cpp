@@ -1,0 +1,453 @@
+// mapper.cpp — vr::Mapper on the device: creation, frame slots, the stitch of one frame and of a batch,
+// timing read-back and the traffic model.  Host orchestration only; the kernels are in the *.hip files.
+#include "mapper.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+namespace octvr {
+
+namespace {
+
+// The RGB(A) result frame of the scaled-output and preview paths (allocated on first use).
+void ensure_result(octvr_mapper& m) {
+    if (m.result.p) return;
+    REQUIRE((uint64_t)m.W * m.H * 4 < 0x7FFFFF80ull, "stitch frame larger than 2 GiB as RGBA");
+    DeviceGuard dg(m.device);
+    // result = 0 (mapper.cpp:156): pixels no camera writes stay black in every frame
+    m.result.alloc((size_t)m.W * m.H * 4);
+    HIP_CHECK(hipMemset(m.result.p, 0, m.result.n));
+    MbCamLevel v{};
+    v.g_off = 0;
+    v.g_pitch = (uint32_t)m.W * 4;
+    v.w = m.W;
+    v.h = m.H;
+    m.result_view.upload(&v, 1);
+}
+
+void check_out_pitch(const octvr_mapper* m, size_t out_pitch) {
+    REQUIRE(out_pitch >= (size_t)m->SW, "output pitch smaller than width");
+    // the stitch kernel addresses the output through a buffer resource with 32-bit offsets
+    REQUIRE((uint64_t)out_pitch * (m->SH + m->SH / 2) < 0x7FFFFF80ull, "output frame larger than 2 GiB");
+}
+
+// The kernels' view of one frame's inputs.
+FrameSet frame_set(const octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch) {
+    FrameSet fs;
+    memset(&fs, 0, sizeof fs);
+    for (int i = 0; i < m->n; i++) fs.f[i] = checked_source_frame(in_dev[i], in_pitch[i], m->in_w[i], m->in_h[i], m->vig[i].p);
+    return fs;
+}
+
+// ---- frame slots -------------------------------------------------------------------------------------
+// One more slot: gains of 1, the feed's totals and tickets and the composite's work queue zeroed.  The
+// caller synchronises the device before a stream uses the slot.
+octvr_mapper::FrameSlot make_slot(octvr_mapper& m) {
+    auto b = std::make_unique<octvr_mapper::SlotBufs>();
+    const std::vector<double> ones(kMaxCams, 1.0);
+    b->gains.upload(ones.data(), ones.size());
+    if (m.use_gain) {
+        b->totals.alloc((size_t)kGainMaxCams * kGainMaxCams * kGainTotalStride);
+        HIP_CHECK(hipMemset(b->totals.p, 0, b->totals.n * sizeof(unsigned long long)));
+        b->tickets.alloc(9);
+        HIP_CHECK(hipMemset(b->tickets.p, 0, b->tickets.n * sizeof(uint32_t)));
+    }
+    if (m.tiles.queue.n) {
+        b->queue.alloc(m.tiles.queue.n);
+        HIP_CHECK(hipMemset(b->queue.p, 0, b->queue.n * sizeof(uint32_t)));
+    }
+    octvr_mapper::FrameSlot sl;
+    sl.gains = b->gains.p;
+    sl.totals = b->totals.p;
+    sl.tickets = b->tickets.p;
+    sl.queue = b->queue.p;
+    m.slot_bufs.push_back(std::move(b));
+    return sl;
+}
+
+// The next slot in turn.  Stitches sharing a frame slot (gains, feed totals, work counters) are ordered:
+// each waits for the slot's previous stitch (with one slot: for the previous stitch, as vr::Mapper is not
+// re-entrant either).  Always through the event, never by comparing stream handles: a destroyed stream's
+// handle value can come back as a new stream that is not ordered after the old one.
+octvr_mapper::FrameSlot& take_slot(octvr_mapper* m, hipStream_t s) {
+    m->cur_slot = (m->cur_slot + 1) % (int)m->slots.size();
+    octvr_mapper::FrameSlot& sl = m->slots[m->cur_slot];
+    if (sl.done) HIP_CHECK(hipStreamWaitEvent(s, sl.done, 0));
+    return sl;
+}
+
+// The slot's stitch has been issued on s.
+void finish_slot(octvr_mapper::FrameSlot& sl, hipStream_t s) {
+    if (!sl.done) HIP_CHECK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(sl.done, s));
+}
+
+// The frame's gains into its slot: copied from another mapper (gains_dev), set (gains, one per input), or
+// estimated by the gain feed (GainCompensatorGPU::feed, exposure_compensate.cpp:223-297).
+void stitch_gains(octvr_mapper* m, octvr_mapper::FrameSlot& sl, const FrameSet& fs, const double* gains,
+                  const double* gains_dev, hipStream_t s) {
+    if (!m->use_gain) return;
+    if (gains_dev) {
+        HIP_CHECK(hipMemcpyAsync(sl.gains, gains_dev, sizeof(double) * m->n, hipMemcpyDeviceToDevice, s));
+    } else if (gains) {
+        HIP_CHECK(launch_set_gains(gains, m->n, sl.gains, s));
+    } else if (m->n_chunks == 0) {  // no intersections: A = diag(b), every gain is 1
+        const std::vector<double> ones(m->n, 1.0);
+        HIP_CHECK(launch_set_gains(ones.data(), m->n, sl.gains, s));
+    } else {
+        // with frames in flight the feed runs beside the previous frame's composite: the lean
+        // variant fits next to it (the wide-prefetch one waits for its workgroups to drain)
+        const bool lean = m->slots.size() > 1;
+        HIP_CHECK(launch_gain_feed(fs, m->samples.p, m->partners.p, m->tex, m->n_chunks, m->N.p, m->n, sl.totals,
+                                   sl.tickets, sl.gains, s, lean, m->pix));
+    }
+}
+
+// The timing events of this stitch, or none (octvr_mapper_set_timing: every `timing`-th stitch)
+std::pair<hipEvent_t, hipEvent_t> stitch_events(octvr_mapper* m) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool timed = m->timing > 0 && (m->timed_calls++ % (uint64_t)m->timing) == 0;
+    if (!timed) return {e0, e1};
+    if (m->free_events.empty()) {
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+    } else {
+        e0 = m->free_events.back().first;
+        e1 = m->free_events.back().second;
+        m->free_events.pop_back();
+    }
+    return {e0, e1};
+}
+
+// The event pair of one stitch: kept with the recorded ones once the launch is issued, else (an exception
+// on the way) returned to the reusable ones.
+struct TimedPair {
+    octvr_mapper* m;
+    hipEvent_t e0, e1;
+    bool kept = false;
+    explicit TimedPair(octvr_mapper* mapper) : m(mapper) {
+        const auto ev = stitch_events(mapper);
+        e0 = ev.first;
+        e1 = ev.second;
+    }
+    TimedPair(const TimedPair&) = delete;
+    void keep() {
+        if (e0) m->events.emplace_back(e0, e1);
+        kept = true;
+    }
+    ~TimedPair() {
+        if (!e0 || kept) return;
+        try {
+            m->free_events.emplace_back(e0, e1);
+        } catch (...) {
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+        }
+    }
+};
+
+}  // namespace
+
+// Mapper::stitch (mapper.cpp:193-323).  gains_dev (device, n doubles): gains of another mapper of the
+// same inputs, copied stream-ordered (AsyncMultiMapper's gain_modes chaining, async.cpp:78-86).
+void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch, uint8_t* out_dev,
+                   size_t out_pitch, const double* gains, int n_gains, const double* gains_dev, hipStream_t s,
+                   const PreviewOut* preview) {
+    REQUIRE(m && in_dev && in_pitch && out_dev, "NULL argument");
+    if (preview) {
+        REQUIRE(preview->dev && preview->w > 0 && preview->h > 0 && preview->pitch >= (size_t)preview->w * 3,
+                "bad preview output");
+        // the preview resizes the whole-frame RGB result, which one frame slot owns
+        REQUIRE(m->slots.size() == 1, "preview output needs one frame in flight");
+        ensure_result(*m);
+    }
+    check_out_pitch(m, out_pitch);
+    DeviceGuard dg(m->device);
+    const FrameSet fs = frame_set(m, in_dev, in_pitch);
+    REQUIRE(!m->use_gain || gains_dev || !gains || n_gains == m->n, "gains must have one entry per input");
+    octvr_mapper::FrameSlot& sl = take_slot(m, s);
+    stitch_gains(m, sl, fs, gains, gains_dev, s);
+    TimedPair ev(m);
+    hipEvent_t e0 = ev.e0, e1 = ev.e1;
+    const bool timed = e0 != nullptr;
+    if (timed && (m->scaled || m->mb || preview)) HIP_CHECK(hipEventRecord(e0, s));  // else the composite records its own
+    if (m->scaled || preview) {
+        // stitch at template size into the RGB(A) result, then resize + RGB -> YUV420P (mapper.cpp:290-306)
+        // (one frame slot only: the result frame is shared); without scaling the resize is the identity
+        if (m->mb)
+            multiband_run(*m->mb, 0, fs, sl.gains, m->use_gain, nullptr, 0, s, m->result.p, (int64_t)m->W * 4, m->pix);
+        else
+            HIP_CHECK(launch_mb_remap(fs, m->tiles.view, sl.gains, m->use_gain,
+                                      RgbaOut{m->result.p, (uint32_t)m->result.n, m->result_view.p}, s, m->pix));
+        HIP_CHECK(launch_resize_rgba_yuv420(m->result.p, m->W, m->H, (int64_t)m->W * 4, out_dev, m->SW, m->SH,
+                                            (int64_t)out_pitch, s, (m->pix & kPixOutNv12) != 0));
+        if (preview)  // cuda::resize(result, preview_output, ...) (mapper.cpp:308-312)
+            HIP_CHECK(launch_resize_rgba_rgb(m->result.p, m->W, m->H, (int64_t)m->W * 4, preview->dev, preview->w,
+                                             preview->h, (int64_t)preview->pitch, s));
+    } else if (m->mb) {
+        multiband_run(*m->mb, m->cur_slot, fs, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s, nullptr, 0, m->pix);
+    } else {
+        TiledLut view = m->tiles.view;
+        view.queue = sl.queue;
+        HIP_CHECK(launch_stitch(fs, view, m->W, m->H, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s, e0, e1,
+                                m->pix));
+    }
+    if (timed && (m->scaled || m->mb || preview)) HIP_CHECK(hipEventRecord(e1, s));
+    ev.keep();
+    finish_slot(sl, s);
+}
+
+// nb frames (1, 2 or 4) of the same rig in one composite launch (FrameBatch, kernels.hpp): each frame's
+// gains into its own frame slot (nb consecutive slots, each waited for as mapper_stitch waits for one),
+// then one pass over the tiled LUT for all of them.  Scaled-output and multi-band / feather mappers have no
+// batched kernel: their frames are stitched one by one.
+void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, const size_t* in_pitch,
+                         uint8_t* const* out_dev, size_t out_pitch, const double* gains, hipStream_t s) {
+    REQUIRE(m && in_dev && in_pitch && out_dev, "NULL argument");
+    REQUIRE(nb == 1 || nb == 2 || nb == 4, "a batch holds 1, 2 or 4 frames");
+    for (int f = 0; f < nb; f++) REQUIRE(out_dev[f], "NULL output");
+    if (nb == 1 || m->scaled || m->mb) {
+        for (int f = 0; f < nb; f++)
+            mapper_stitch(m, in_dev + (size_t)f * m->n, in_pitch + (size_t)f * m->n, out_dev[f], out_pitch,
+                          gains ? gains + (size_t)f * m->n : nullptr, gains ? m->n : 0, nullptr, s);
+        return;
+    }
+    REQUIRE((int)m->slots.size() >= nb, "a batch of n frames needs n frames in flight (octvr_mapper_set_frames_in_flight)");
+    REQUIRE(nb <= 2 || m->n <= 16, "a batch of 4 frames holds 16 cameras per frame");
+    check_out_pitch(m, out_pitch);
+    DeviceGuard dg(m->device);
+    FrameSet fs[kMaxBatch];  // every frame checked before any of them puts work on the stream
+    for (int f = 0; f < nb; f++) fs[f] = frame_set(m, in_dev + (size_t)f * m->n, in_pitch + (size_t)f * m->n);
+    const double* g[kMaxBatch];
+    octvr_mapper::FrameSlot* sl[kMaxBatch];
+    const bool feed = m->use_gain && !gains && m->n_chunks > 0;  // every frame's gains estimated: one feed launch
+    unsigned long long* tot[kMaxBatch];
+    uint32_t* tick[kMaxBatch];
+    double* gd[kMaxBatch];
+    for (int f = 0; f < nb; f++) {
+        sl[f] = &take_slot(m, s);
+        if (!feed) stitch_gains(m, *sl[f], fs[f], gains ? gains + (size_t)f * m->n : nullptr, nullptr, s);
+        g[f] = sl[f]->gains;
+        tot[f] = sl[f]->totals;
+        tick[f] = sl[f]->tickets;
+        gd[f] = sl[f]->gains;
+    }
+    if (feed)  // GainCompensatorGPU::feed of each frame (exposure_compensate.cpp:223-297), all in one launch
+        HIP_CHECK(launch_gain_feed_batch(fs, nb, m->samples.p, m->partners.p, m->tex, m->n_chunks, m->N.p, m->n, tot, tick,
+                                         gd, s, true, m->pix));
+    TimedPair ev(m);
+    TiledLut view = m->tiles.view;
+    view.queue = sl[0]->queue;  // this launch's work counters (the first frame's slot)
+    HIP_CHECK(launch_stitch_batch(fs, nb, view, m->W, m->H, g, m->use_gain, out_dev, (int64_t)out_pitch, s, ev.e0, ev.e1,
+                                  m->pix));
+    ev.keep();
+    for (int f = 0; f < nb; f++) finish_slot(*sl[f], s);
+}
+
+int mapper_num_inputs(const octvr_mapper* m) { return m->n; }
+bool mapper_has_gain(const octvr_mapper* m) { return m->use_gain != 0; }
+const double* mapper_gains_dev(const octvr_mapper* m) { return m->slots[m->cur_slot].gains; }
+const SourceFootprint& mapper_footprint(const octvr_mapper* m) { return m->foot; }
+void mapper_out_size(const octvr_mapper* m, int* w, int* h) {
+    *w = m->SW;
+    *h = m->SH;
+}
+
+SourceFrame checked_source_frame(const uint8_t* ptr, size_t pitch, int w, int h, const float* vig) {
+    REQUIRE(ptr && pitch >= (size_t)w, "bad input frame");
+    // the staging loads form row offsets with 24-bit multiplies (composite.hip stage_load)
+    REQUIRE(pitch < ((size_t)1 << 24), "input pitch must be below 16 MiB");
+    // the gain feed reads frames through 32-bit buffer resources
+    REQUIRE((uint64_t)pitch * (uint64_t)(h + h / 2) < 0x7FFFFFFFull, "input frame larger than 2 GiB");
+    // ... in 8-byte segments (gain_feed.hip feed_taps_issue)
+    REQUIRE((uint64_t)pitch * (uint64_t)(h + h / 2) >= 8, "input frame below 8 bytes");
+    return SourceFrame{ptr, w, h, (int64_t)pitch, vig};
+}
+
+TiledLutBuild build_frame_tiles(const std::vector<CompositeEntry>& lut, int W, int H, const std::vector<int>& in_w,
+                                const std::vector<int>& in_h, int* n_jobs) {
+    // items of 128 x 16 (two quads per lane, OCTVR_QPL) for the per-frame composite
+    const int qpl = composite_qpl();
+    const int tx_n = (W + kTileW - 1) / kTileW, ty_n = (H + kTileH * qpl - 1) / (kTileH * qpl);
+    std::vector<TileJob> jobs;
+    jobs.reserve((size_t)tx_n * ty_n);
+    for (int ty = 0; ty < ty_n; ty++)
+        for (int tx = 0; tx < tx_n; tx++) jobs.push_back(TileJob{tx, ty, 0});
+    if (n_jobs) *n_jobs = tx_n * ty_n;
+    // build_tiled_lut checks that every tap of every pixel lies in a staged group of its slot
+    return build_tiled_lut(jobs, [&](int, int x, int y) {
+        return (x < W && y < H) ? lut[(size_t)y * W + x] : CompositeEntry{0u, 0u};
+    }, in_w, in_h, qpl);
+}
+
+std::unique_ptr<octvr_mapper> mapper_create(const octvr_rig* rig, int device, int n_inputs, const int* in_w,
+                                            const int* in_h, int blend, int enable_gain, int scale_w, int scale_h,
+                                            int flags) {
+    REQUIRE(rig && in_w && in_h, "NULL argument");
+    REQUIRE((flags & ~OCTVR_REMAP_TEXTURE) == 0, "unknown mapper flags");
+    if (!rig->overlays.empty())  // checked first: the real reason, whatever n_inputs says
+        throw OctvrError(OCTVR_E_UNSUPPORTED, "overlay inputs are not implemented in this ABI version");
+    REQUIRE(n_inputs == (int)rig->inputs.size(), "in_sizes must cover every input");
+    REQUIRE((int)rig->inputs.size() <= kMaxCams, "too many inputs");
+    REQUIRE(scale_w >= 0 && scale_h >= 0 && (scale_w == 0) == (scale_h == 0), "bad scaled output size");
+    REQUIRE(rig->out_w % 2 == 0 && rig->out_h % 2 == 0, "YUV420 output needs even width/height");
+    auto m = std::make_unique<octvr_mapper>();
+    m->device = device;
+    m->tex = (flags & OCTVR_REMAP_TEXTURE) ? 1 : 0;
+    m->n = (int)rig->inputs.size();
+    m->W = rig->out_w;
+    m->H = rig->out_h;
+    // scaled_output_size = scale_output.area() == 0 ? mt.out_size : scale_output (mapper.cpp:69)
+    m->SW = scale_w ? scale_w : m->W;
+    m->SH = scale_h ? scale_h : m->H;
+    REQUIRE(m->SW % 2 == 0 && m->SH % 2 == 0, "YUV420 output needs even width/height");
+    m->scaled = m->SW != m->W || m->SH != m->H;
+    REQUIRE(!m->scaled || (uint64_t)m->W * m->H * 4 < 0x7FFFFF80ull, "stitch frame larger than 2 GiB as RGBA");
+    m->in_w.assign(in_w, in_w + n_inputs);
+    m->in_h.assign(in_h, in_h + n_inputs);
+    for (int i = 0; i < m->n; i++)
+        REQUIRE(m->in_w[i] > 0 && m->in_h[i] > 0 && m->in_w[i] % 2 == 0 && m->in_h[i] % 2 == 0 &&
+                    m->in_w[i] <= 65535 && m->in_h[i] <= 65535,
+                "input sizes must be even and < 65536");
+    // mapper.cpp:78-82: a single input disables gain (and blend)
+    m->use_gain = (enable_gain && m->n > 1) ? 1 : 0;
+    m->blend = m->n > 1 ? blend : 0;
+    REQUIRE(!m->use_gain || m->n <= 16, "gain estimation supports at most 16 inputs");
+    DeviceGuard dg(device);
+    // vignette: cv::cuda::resize(vignette, vignette_maps[i], in_size) (mapper.cpp:108-112), applied to
+    // every source pixel before the remap (mapper.cpp:230-231)
+    m->vig.resize(m->n);
+    for (int i = 0; i < m->n; i++) {
+        const RigInput& in = rig->inputs[i];
+        if (in.vignette.empty()) continue;
+        const std::vector<float> v = resize_linear_f32(in.vignette.data(), in.vig_w, in.vig_h, m->in_w[i], m->in_h[i]);
+        m->vig[i].upload(v.data(), v.size());
+    }
+    m->foot.init(m->in_w, m->in_h);
+    if (m->blend > 0) {
+        // MultiBandGPUBlender(seam_masks, rois, bands), bands = ceil(log2(blend)) - 1 (mapper.cpp:171-176)
+        const int bands = (int)(std::ceil(std::log((double)m->blend) / std::log(2.)) - 1.);
+        m->mb.reset(multiband_create(*rig, device, bands, m->in_w, m->in_h, 0, &m->foot, m->tex));
+    } else if (m->blend < 0) {
+        // FeatherGPUBlender(masks, rois, border = -blend) (mapper.cpp:177-182)
+        m->mb.reset(multiband_create(*rig, device, 0, m->in_w, m->in_h, -m->blend, &m->foot, m->tex));
+    } else {
+        // per-camera templates -> device, composite LUT, then drop the per-camera maps
+        std::vector<DevBuf<float>> m1(m->n), m2(m->n);
+        std::vector<DevBuf<uint8_t>> mk(m->n);
+        std::vector<CamTemplate> ct(m->n);
+        for (int i = 0; i < m->n; i++) {
+            const RigInput& in = rig->inputs[i];
+            m1[i].upload(in.map1.data(), in.map1.size());
+            m2[i].upload(in.map2.data(), in.map2.size());
+            mk[i].upload(in.mask.data(), in.mask.size());
+            ct[i] = CamTemplate{m1[i].p, m2[i].p, mk[i].p, in.roi[0], in.roi[1], in.roi[2], in.roi[3],
+                                m->in_w[i], m->in_h[i]};
+        }
+        DevBuf<CamTemplate> ctd;
+        ctd.upload(ct.data(), ct.size());
+        DevBuf<CompositeEntry> lut;
+        lut.alloc((size_t)m->W * m->H);
+        HIP_CHECK(launch_composite_lut(ctd.p, m->n, m->W, m->H, lut.p, nullptr, m->tex));
+        HIP_CHECK(hipDeviceSynchronize());
+        std::vector<CompositeEntry> lut8((size_t)m->W * m->H);
+        HIP_CHECK(hipMemcpy(lut8.data(), lut.p, lut8.size() * sizeof(CompositeEntry), hipMemcpyDeviceToHost));
+        lut.reset();
+        for (int i = 0; i < m->n; i++) {
+            m1[i].reset();
+            m2[i].reset();
+            mk[i].reset();
+        }
+        const TiledLutBuild tb = build_frame_tiles(lut8, m->W, m->H, m->in_w, m->in_h, &m->n_tiles);
+        footprint_add_tiles(m->foot, tb);
+        m->tiles.upload(tb);
+    }
+    if (m->scaled) ensure_result(*m);
+    m->last_gains.assign(m->n, 1.0);
+    if (m->use_gain) setup_gain(*m, *rig);
+    m->slots.push_back(make_slot(*m));
+    HIP_CHECK(hipDeviceSynchronize());  // the slot's memsets complete before any stream uses it
+    return m;
+}
+
+void mapper_sync(octvr_mapper& m) {
+    for (auto& sl : m.slots)
+        if (sl.done) HIP_CHECK(hipEventSynchronize(sl.done));
+}
+
+void mapper_set_frames_in_flight(octvr_mapper* m, int k) {
+    REQUIRE(m && k >= 1 && k <= OCTVR_MAX_FRAMES_IN_FLIGHT, "frames in flight must be 1..OCTVR_MAX_FRAMES_IN_FLIGHT");
+    if (k > 1 && m->scaled)
+        throw OctvrError(OCTVR_E_UNSUPPORTED, "frames in flight > 1 need the output at template size (no scaled output)");
+    DeviceGuard dg(m->device);
+    mapper_sync(*m);
+    if (m->cur_slot != 0) {  // keep the last frame's gains for gains() / chaining
+        HIP_CHECK(hipMemcpy(m->slots[0].gains, m->slots[m->cur_slot].gains, sizeof(double) * m->n,
+                            hipMemcpyDeviceToDevice));
+        m->cur_slot = 0;
+    }
+    for (size_t i = 1; i < m->slots.size(); i++)
+        if (m->slots[i].done) (void)hipEventDestroy(m->slots[i].done);
+    m->slots.resize(1);
+    m->slot_bufs.resize(1);
+    for (int i = 1; i < k; i++) m->slots.push_back(make_slot(*m));
+    if (m->mb) multiband_set_slots(*m->mb, k);
+    HIP_CHECK(hipDeviceSynchronize());  // the memsets complete before any stream uses the slots
+}
+
+void mapper_set_timing(octvr_mapper* m, int enable) {
+    REQUIRE(m && enable >= 0, "bad arguments");
+    m->timing = enable;
+    m->timed_calls = 0;
+    if (enable) {
+        // the event pairs of the next timed stitches created now, not inside the caller's timed region
+        // (hipEventCreate there cost the 20-step bench region ~20 us of host time per step)
+        DeviceGuard dg(m->device);
+        constexpr size_t kEventReserve = 1024;
+        while (m->free_events.size() + m->events.size() < kEventReserve) {
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            HIP_CHECK(hipEventCreate(&e0));
+            const hipError_t e = hipEventCreate(&e1);
+            if (e != hipSuccess) (void)hipEventDestroy(e0);
+            HIP_CHECK(e);
+            m->free_events.emplace_back(e0, e1);
+        }
+    }
+}
+
+int mapper_drain_timing(octvr_mapper* m, const std::function<void(double, double)>& f) {
+    DeviceGuard dg(m->device);
+    for (auto& e : m->events) {
+        HIP_CHECK(hipEventSynchronize(e.second));
+        float start = 0, len = 0;
+        HIP_CHECK(hipEventElapsedTime(&start, m->events[0].first, e.first));
+        HIP_CHECK(hipEventElapsedTime(&len, e.first, e.second));
+        f((double)start, (double)start + (double)len);
+    }
+    const int launches = (int)m->events.size();
+    m->free_events.insert(m->free_events.end(), m->events.begin(), m->events.end());
+    m->events.clear();
+    return launches;
+}
+
+// The bytes of the tiled LUT one pass of the composite reads: 4 B entries (3 B packed, 8 B in wide tiles),
+// tile headers / slots.
+double tiled_lut_bytes(const TiledLut& t) {
+    return (t.e24 ? 3.0 : 4.0) * t.n_items * kTilePx * t.qpl + 8.0 * t.n_wide * kTilePx +
+           (double)t.n_items * (sizeof(TileHdr) + kTileSlots * sizeof(TileSlot)) + 4.0 * t.n_wide;
+}
+
+double mapper_traffic(const octvr_mapper* m) {
+    // composite kernel: 4 B tiled-LUT entry (8 B in wide tiles) + 1.5 B YUV420 output per output
+    // pixel, the unique source bytes its staged boxes cover (YUV420P, 1.5 B per luma pixel: the
+    // circular crops leave the rest of each frame unread), tile headers / slots.  Multi-band: the
+    // sum over the sequence's launches (multiband_traffic_parts).
+    if (m->mb) return multiband_traffic(*m->mb);
+    return tiled_lut_bytes(m->tiles.view) + 1.5 * m->W * m->H + m->tiles.source_bytes;
+}
+
+}  // namespace octvr

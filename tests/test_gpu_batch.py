@@ -135,6 +135,44 @@ def test_gpu_batch_vignette(ox):
         assert np.array_equal(outs[f].cpu().numpy(), want), f
 
 
+def test_gpu_batch_rejects_late_bad_frame(ox):
+    """A batch whose second frame is bad (camera 0's pitch below its width) is rejected with OCTVR_E_INVALID
+    before any frame puts work on the stream: the batches after it on the same mapper and stream equal the
+    oracle bit for bit (outputs and last gains: the slot rotation is undisturbed), and the timed launches
+    are exactly theirs (no event pair lost to the rejected call)."""
+    import torch
+    from octvr_amd import synthetic
+    n, in_w, in_h, W, H = 3, 320, 240, 512, 256
+    mt = ox.MapperTemplate.from_json(json.dumps(_ring_rig(n, in_w, in_h)), W, H)
+    sizes = [(in_w, in_h)] * n
+    rois, maps1, maps2, masks = _template(mt, n)
+    m = ox.Mapper(mt, sizes, blend=0, enable_gain=True)
+    m.set_frames_in_flight(4)
+    frames = [[synthetic.smooth_yuv_frame(w, h, 300 + 11 * f + i) for i, (w, h) in enumerate(sizes)] for f in range(4)]
+    dev = [[_cuda(x) for x in fr] for fr in frames]
+    outs = [torch.zeros((H * 3 // 2, W), dtype=torch.uint8, device="cuda") for _ in range(4)]
+    st = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    bad = m.batch_refs(dev[:2], outs[:2])
+    bad.pitches[n] = in_w - 1  # frame 1, camera 0
+    with pytest.raises(ox.OctvrError) as err:
+        m.stitch_batch(bad, stream=st)
+    assert err.value.code == ox.E_INVALID
+    m.set_timing(True)
+    for b in range(2):
+        m.stitch_batch(dev[2 * b:2 * b + 2], outs[2 * b:2 * b + 2], stream=st)
+    g_last = np.array(m.gains())
+    torch.cuda.synchronize()
+    assert len(m.kernel_intervals()) == 2
+    for f in range(4):
+        want, g_orc = O.stitch_frame(frames[f], sizes, rois, maps1, maps2, masks, W, H, enable_gain=True, gains=None,
+                                     threads=8)
+        got = outs[f].cpu().numpy()
+        assert np.array_equal(got, want), (f, int((got != want).sum()))
+        if f == 3:
+            np.testing.assert_array_equal(g_last, np.array(g_orc))
+
+
 def test_gpu_batch_rejects(ox):
     import torch
     rig = _ring_rig(20)

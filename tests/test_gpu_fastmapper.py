@@ -87,6 +87,38 @@ def test_gpu_fastmapper_edge_taps(product_lib):
         assert want.any()
 
 
+def test_fastmapper_stitch_rejects_bad_frame(product_lib):
+    """An input whose pitch is below its width is refused with OCTVR_E_INVALID and the Mapper's wording
+    ("bad input frame": the two share the frame check) before anything is launched; the valid stitch after
+    it is bit-exact vs the oracle."""
+    import torch
+    ox = product_lib
+    W, H = 96, 48
+    sizes = [(40, 24), (42, 26)]
+    rng = np.random.default_rng(17)
+    m1 = [rng.uniform(0.0, 1.0, (H, W)).astype(np.float32) for _ in sizes]
+    m2 = [rng.uniform(0.0, 1.0, (H, W)).astype(np.float32) for _ in sizes]
+    mk = [np.full((H, W), 255, np.uint8) for _ in sizes]
+    mk[1][:, : W // 3] = 0
+    mt = ox.MapperTemplate.from_arrays(W, H, [[0, 0, W, H]] * 2, m1, m2, mk)
+    fm = ox.FastMapper(mt, sizes)
+    frames = [O.rand_img(w, h * 3 // 2, 1, 170 + i) for i, (w, h) in enumerate(sizes)]
+    out = torch.zeros((H * 3 // 2, W), dtype=torch.uint8, device="cuda")
+    bad = ox.Mapper.frame_refs([torch.from_numpy(f).cuda() for f in frames])
+    bad.pitches[1] = sizes[1][0] - 1
+    with pytest.raises(ox.OctvrError) as err:
+        fm.stitch_nv12(bad, out)
+    assert err.value.code == ox.E_INVALID
+    assert ox.lib().octvr_last_error().decode() == "bad input frame"
+    fm.stitch_nv12([torch.from_numpy(f).cuda() for f in frames], out)
+    torch.cuda.synchronize()
+    want = O.fastmapper_nv12(frames, sizes, m1, m2, mk, W, H)
+    got = out.cpu().numpy()
+    d = got != want
+    assert not d.any(), (int(d.sum()), np.argwhere(d)[:5].tolist())
+    assert want.any()
+
+
 def test_gpu_fastmapper_wide_blocks(product_lib):
     """A 4000-pixel-wide source sampled at random over a 96-pixel output: a luma block's taps span more
     than 2048 pixels, so the Y plane falls back to the 8-byte entries, while the half-size chroma plane

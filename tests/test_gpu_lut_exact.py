@@ -3,7 +3,7 @@
 The FP64 LUT kernel evaluates every pixel with device libm (OCML); where a last-ulp difference from
 glibc could change the outcome (a branch threshold, the [0, 1) test, a mask index, the f32 rounding),
 its guard defers the pixel to the host, which recomputes it with glibc (camera_math.hpp LutGuard,
-octvr_hip.cpp build_input).  These tests
+rig_json.cpp build_input).  These tests
   * measure the device-vs-glibc deviation of the FP64 projection on every model and check that the
     guard's tolerance covers it with a wide margin (every non-deferred pixel rounds identically);
   * require the whole LUT (ROI, map1, map2, mask, include-mask arbitration) to equal the oracle's bit

@@ -1,5 +1,5 @@
 """The host half of the bit-exact LUT build (no GPU): pixels the GPU's LUT guard defers are recomputed
-on the host with glibc by the product's own camera_math.hpp (octvr_hip.cpp build_input).  That host
+on the host with glibc by the product's own camera_math.hpp (rig_json.cpp build_input).  That host
 projection must equal the oracle's FP64 projection bit for bit (the oracle is pinned to the reference's
 LUT goldens, tests/test_oracle_golden.py), for every camera model and mask kind the guard covers."""
 import json
