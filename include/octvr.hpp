@@ -553,6 +553,14 @@ public:
     virtual void push(std::vector<std::tuple<cv::Mat, cv::Mat, cv::Mat>>& inputs,
                       std::tuple<cv::Mat, cv::Mat, cv::Mat>& output) = 0;
     virtual void pop() = 0;
+    // Not in the reference: the pixel layouts of the host planes, OCTVR_PIX_YUV420P (the default) or
+    // OCTVR_PIX_NV12, for the inputs (all alike) and the output independently (octvr_hip.h
+    // octvr_async_set_pixel_formats; no frame may be pending).  With NV12 the second cv::Mat of an input or
+    // output tuple is the interleaved U,V plane — CV_8UC1 of W x H/2 or CV_8UC2 of W/2 x H/2 — and the third
+    // may be empty.
+    virtual void set_pixel_formats(int in_format, int out_format) = 0;
+    // Not in the reference: the formats in use.
+    virtual void pixel_formats(int& in_format, int& out_format) const = 0;
     // Not in the reference: the latest published preview (CV_8UC3, preview_size) and its header; false
     // before the first frame completes.  Throws without a preview.
     virtual bool preview(cv::Mat& rgb, PreviewDataHeader& hdr) = 0;
@@ -583,6 +591,9 @@ public:
         std::vector<double> reg;
         for (const cv::Rect_<double>& r : output_regions) reg.insert(reg.end(), {r.x, r.y, r.width, r.height});
         n_ = (int)in_sizes.size();
+        w_ = w;
+        h_ = h;
+        out_size_ = out_size;
         octvr_async* a = nullptr;
         check(octvr_async_create_preview(rp.data(), (int)k, device(), n_, w.data(), h.data(), out_size.width,
                                          out_size.height, blend_modes.data(), gain_modes.data(), reg.data(), flags,
@@ -602,16 +613,21 @@ public:
     void push(std::vector<std::tuple<cv::Mat, cv::Mat, cv::Mat>>& inputs,
               std::tuple<cv::Mat, cv::Mat, cv::Mat>& output) override {
         if ((int)inputs.size() != n_) throw cv::Exception(OCTVR_E_INVALID, "input count does not match");
+        int fi = 0, fo = 0;
+        check(octvr_async_pixel_formats(a_, &fi, &fo));
         std::vector<const uint8_t*> in;
         std::vector<size_t> ip;
         Held hold;
-        for (auto& t : inputs) {
+        for (size_t i = 0; i < inputs.size(); i++) {
+            auto& t = inputs[i];
+            if (fi == OCTVR_PIX_NV12) check_uv(std::get<1>(t), w_[i], h_[i], "input");
             for (const cv::Mat* m : {&std::get<0>(t), &std::get<1>(t), &std::get<2>(t)}) {
                 in.push_back(m->data);
                 ip.push_back(m->step);
                 hold.push_back(*m);  // the caller's buffers must stay alive until pop (refcounted headers)
             }
         }
+        if (fo == OCTVR_PIX_NV12) check_uv(std::get<1>(output), out_size_.width, out_size_.height, "output");
         uint8_t* out[3] = {std::get<0>(output).data, std::get<1>(output).data, std::get<2>(output).data};
         size_t op[3] = {std::get<0>(output).step, std::get<1>(output).step, std::get<2>(output).step};
         hold.push_back(std::get<0>(output));
@@ -624,6 +640,12 @@ public:
         const int rc = octvr_async_pop(a_);
         if (!held_.empty()) held_.pop_front();
         check(rc);
+    }
+    void set_pixel_formats(int in_format, int out_format) override {
+        check(octvr_async_set_pixel_formats(a_, in_format, out_format));
+    }
+    void pixel_formats(int& in_format, int& out_format) const override {
+        check(octvr_async_pixel_formats(a_, &in_format, &out_format));
     }
     bool preview(cv::Mat& rgb, PreviewDataHeader& hdr) override {
         if (preview_size_.area() == 0) throw cv::Exception(OCTVR_E_INVALID, "no preview (preview_size 0)");
@@ -666,7 +688,17 @@ private:
     }
     std::unique_ptr<QtZones> qt_;
 #endif
+    // an NV12 side's U,V plane of a w x h frame: w bytes x h/2 rows, as CV_8UC1 (w columns) or CV_8UC2 (w/2)
+    static void check_uv(const cv::Mat& m, int w, int h, const char* what) {
+        const bool ok = !m.empty() && m.rows == h / 2 &&
+                        ((m.type() == CV_8UC1 && m.cols == w) || (m.type() == CV_8UC2 && m.cols == w / 2));
+        if (!ok)
+            throw cv::Exception(OCTVR_E_INVALID, std::string("NV12 ") + what +
+                                                     ": the U,V plane must be CV_8UC1 of W x H/2 or CV_8UC2 of W/2 x H/2");
+    }
     typedef std::vector<cv::Mat> Held;
+    std::vector<int> w_, h_;
+    cv::Size out_size_;
     cv::Size preview_size_;
     octvr_async* a_ = nullptr;
     int n_ = 0;

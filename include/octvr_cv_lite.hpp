@@ -5,7 +5,7 @@
  * map.cpp, the AsyncMultiMapper caller) touch:
  *   cv::Size, cv::Point / Point2d, cv::Rect / Rect_<double>, cv::Vec6f, cv::Mat, cv::UMat (host
  *   memory here: the reference's OpenCL UMat path is replaced by HIP behind the C ABI),
- *   cv::cuda::GpuMat (HIP device memory), cv::Exception, CV_8UC1 / CV_8UC3 / CV_8UC4 / CV_32FC1.
+ *   cv::cuda::GpuMat (HIP device memory), cv::Exception, CV_8UC1 / CV_8UC2 / CV_8UC3 / CV_8UC4 / CV_32FC1.
  * Mats are reference counted and share data on copy, as OpenCV's do (opencv2/core/mat.hpp).
  */
 #ifndef OCTVR_CV_LITE_HPP
@@ -31,6 +31,7 @@
 #define CV_32F 5
 #define CV_64F 6
 #define CV_8UC1 CV_MAKETYPE(CV_8U, 1)
+#define CV_8UC2 CV_MAKETYPE(CV_8U, 2)
 #define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
 #define CV_8UC4 CV_MAKETYPE(CV_8U, 4)
 #define CV_32FC1 CV_MAKETYPE(CV_32F, 1)

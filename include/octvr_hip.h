@@ -201,7 +201,8 @@ int octvr_mapper_set_frames_in_flight(octvr_mapper* mapper, int k);
  * independent; `pitch` rules are unchanged (>= W, any alignment).  The kernels read and write the layouts
  * themselves (no conversion pass, no intermediate frame): the result is the planar stitch of the same
  * pixels, bit for bit, with the chroma bytes rearranged.  Any other value: OCTVR_E_INVALID.  Synchronizes.
- * The octvr_async_* pipeline and the FastMapper are not affected. */
+ * The octvr_async_* pipeline has its own setter, octvr_async_set_pixel_formats, which sets its mappers' formats
+ * through this one; the FastMapper is not affected. */
 enum { OCTVR_PIX_YUV420P = 0, OCTVR_PIX_NV12 = 1 };
 int octvr_mapper_set_pixel_formats(octvr_mapper* mapper, int in_format, int out_format);
 int octvr_mapper_pixel_formats(const octvr_mapper* mapper, int* in_format, int* out_format);
@@ -282,12 +283,35 @@ int octvr_async_pop_preview(octvr_async* async, uint8_t* rgb, size_t pitch, octv
 typedef void (*octvr_preview_sink)(void* user, const uint8_t* rgb, size_t pitch, const octvr_preview_header* hdr);
 int octvr_async_set_preview_sink(octvr_async* async, octvr_preview_sink sink, void* user);
 /* Build-time facts of the pipeline as a JSON object: packed_bytes (the footprint bytes uploaded per frame,
- * run gaps included), runs, frame bytes, preview size, the mappers' creation flags. */
+ * run gaps included), runs, frame bytes, preview size, the mappers' creation flags, and "pixel_formats":
+ * [in, out], the current OCTVR_PIX_* pair. */
 int octvr_async_info(const octvr_async* async, char* buf, size_t len);
+/* Pixel layouts of the pipeline's host planes (no reference counterpart: the reference's planes are planar;
+ * decoders, capture cards and encoders speak NV12): OCTVR_PIX_YUV420P (the default) or OCTVR_PIX_NV12, for the
+ * inputs (all alike) and for the merged output independently — all four pairs are valid.  The array shapes of
+ * push and register_output do not change; with NV12
+ *   inputs:  in_planes[3*i] = Y (W x H), in_planes[3*i+1] = the interleaved U,V plane (W bytes x H/2 rows, U
+ *            first, pitch >= W), in_planes[3*i+2] is ignored and may be NULL;
+ *   output:  out_planes[0] = Y, out_planes[1] = the U,V plane (out_w bytes x out_h/2 rows, pitch >= out_w),
+ *            out_planes[2] is ignored and may be NULL;
+ * and push, register_output, unregister_output and the registered-set match compare only the planes the format
+ * uses.  The formats are forwarded to every mapper (octvr_mapper_set_pixel_formats: the kernels read and write
+ * NV12 themselves), the copy-in packs a run's U,V row in place of its U and V rows (same bytes per run: the
+ * footprint runs are not rebuilt), a kernel of its own unpacks them into NV12 device frames, and the
+ * download / copy-out move a region's Y and U,V rows.  The merged NV12 output is the merged planar output of
+ * the same pixels, bit for bit, with the chroma bytes rearranged: region k's chroma lands at its chroma
+ * rectangle c read in pair units, bytes [2 c.x, 2 c.x + 2 c.w) of the U,V plane's rows [c.y, c.y + c.h); bytes
+ * outside every region, and between a plane's width and its pitch, are never written.  The preview stays RGB.
+ * OCTVR_E_INVALID: any other value; frames pending; a change of the output format while output plane sets are
+ * registered (their plane count and geometry depend on it).  A pipeline on which this was never called behaves
+ * exactly as before.  Synchronizes. */
+int octvr_async_set_pixel_formats(octvr_async* async, int in_format, int out_format);
+int octvr_async_pixel_formats(const octvr_async* async, int* in_format, int* out_format);
 /* push(inputs, output) (async.cpp:174-189): in_planes[3*i+0/1/2] = Y, U, V host planes of input i
  * (W x H, W/2 x H/2, W/2 x H/2) with row pitches in_pitches[3*i+k]; out_planes[0/1/2] / out_pitches: the
- * merged output's Y (out_w x out_h), U and V (out_w/2 x out_h/2) planes.  Returns once the frame is queued;
- * all planes must stay valid until the matching pop. */
+ * merged output's Y (out_w x out_h), U and V (out_w/2 x out_h/2) planes (NV12 sides: Y, U,V, unused — see
+ * octvr_async_set_pixel_formats).  Returns once the frame is queued; all planes must stay valid until the
+ * matching pop. */
 int octvr_async_push(octvr_async* async, const uint8_t* const* in_planes, const size_t* in_pitches,
                      uint8_t* const* out_planes, const size_t* out_pitches);
 /* pop() (async.cpp:191-193): blocks until the oldest pushed frame has been written to its output planes;
@@ -298,7 +322,10 @@ int octvr_async_pop(octvr_async* async);
  * page-locked (hipHostRegister) and every later push with exactly these pointers and pitches is downloaded
  * straight into them — no pinned staging, no host copy-out.  The planes must stay allocated until
  * octvr_async_unregister_output or octvr_async_destroy.  OCTVR_E_HIP if the memory cannot be locked (the
- * planes then keep the staging path). */
+ * planes then keep the staging path).  Planes whose page-rounded byte ranges touch or overlap — one contiguous
+ * NV12 frame registered as (Y = its first out_h rows, U,V = the rows after), or U and V as the two column
+ * halves of one array — are locked once, as one merged range; planes in separate allocations each get their
+ * own hipHostRegister, as before. */
 int octvr_async_register_output(octvr_async* async, uint8_t* const* planes, const size_t* pitches);
 /* Undo octvr_async_register_output (no frame may be pending). */
 int octvr_async_unregister_output(octvr_async* async, uint8_t* const* planes);
@@ -386,6 +413,14 @@ int octvr_debug_gain_plan(const octvr_rig* rig, int n_inputs, const int* in_w, c
  * of an array), parsed with rapidjson's rules (flags 0, as the reference reads its configs) or correctly
  * rounded (OCTVR_JSON_EXACT; out-of-range literals give +-HUGE_VAL / the subnormal / 0 as strtod). */
 int octvr_debug_json_number(const char* json, int flags, double* value);
+/* The AsyncMultiMapper copy-in's packing on caller-given runs (host only, no GPU): run k = runs[4k .. 4k+3] =
+ * (camera, row pair, first 8-pixel group, groups) of cameras of in_w x in_h pixels, packed back to back into
+ * `packed` (capacity cap) by the function the pipeline's copy-in stage calls, from planes / pitches laid out as
+ * octvr_async_push's in_planes / in_pitches for `format` (OCTVR_PIX_*).  sizes[k] (optional) receives run k's
+ * packed bytes, *bytes the total.  OCTVR_E_INVALID for a run outside its frame, a bad plane or a short buffer. */
+int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const uint32_t* runs, int n_runs,
+                          const uint8_t* const* planes, const size_t* pitches, int format, uint8_t* packed, size_t cap,
+                          size_t* sizes, size_t* bytes);
 /* The host build's worker threads (tiler, seam finder, blender weights, audits) on n_threads threads of
  * which thread `failing` raises an error (test hook, no GPU): the error reaches the caller as a status
  * (OCTVR_E_INVALID + octvr_last_error) instead of terminating the process; failing < 0 = none fails. */

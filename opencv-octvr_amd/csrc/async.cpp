@@ -23,7 +23,9 @@
 //     copy-out for them; other planes take the staging path;
 //   * the preview (async.cpp:73-110, 141-171) is published to a caller-read buffer and an optional sink
 //     (octvr_async_pop_preview / octvr_async_set_preview_sink) instead of Qt shared memory, which stays
-//     the caller's.
+//     the caller's;
+//   * the host planes may be NV12 on either side (octvr_async_set_pixel_formats): the mappers read and write
+//     that layout themselves, and every stage here moves a Y plane and one U,V plane instead of three planes.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -38,7 +40,10 @@
 #include <thread>
 #include <vector>
 
+#include <unistd.h>
+
 #include "abi_guard.hpp"
+#include "async_host.hpp"
 #include "mapper.hpp"
 
 using namespace octvr;
@@ -107,7 +112,8 @@ struct PinnedBuf {
     }
 };
 
-struct Slot {  // one frame's buffers: the packed footprint runs, the device frames ("Y over [U|V]", pitch = width)
+struct Slot {  // one frame's buffers: the packed footprint runs, the device frames ("Y over [U|V]", or with NV12
+              // "Y over U,V pairs"; pitch = width)
     std::unique_ptr<PinnedBuf> packed_host;
     DevBuf<uint8_t> packed_dev;
     DevBuf<uint8_t> preview_dev;  // preview_w x preview_h RGB, black outside the regions (async.cpp:314-316)
@@ -118,7 +124,9 @@ struct Slot {  // one frame's buffers: the packed footprint runs, the device fra
 };
 
 // Runs of the union of the mappers' footprints: per camera and row pair, consecutive set groups, gaps of
-// up to kRunGap groups bridged (a few more bytes for fewer, longer copies)
+// up to kRunGap groups bridged (a few more bytes for fewer, longer copies).  A cell (row pair r, group g) is
+// the same pixels in either input layout, and with an even width a run's NV12 chroma row (yb bytes at byte
+// 8 g0) is as long as its planar U and V rows together (2 cb): offsets and sizes hold for both layouts.
 constexpr int kRunGap = 2;
 std::vector<FootRun> footprint_runs(const SourceFootprint& f, size_t& bytes) {
     std::vector<FootRun> runs;
@@ -250,6 +258,10 @@ struct octvr_async {
     std::vector<int> gain_modes;
     std::vector<Rect> regions, regions_uv;  // per mapper: its rectangle in the Y and in the U / V planes
     int flags = 0;
+    // layouts of the host planes (octvr_async_set_pixel_formats); the mappers carry the same pair.  Written by
+    // the caller's thread with no frame pending, read by the stages while a frame is
+    int in_fmt = OCTVR_PIX_YUV420P, out_fmt = OCTVR_PIX_YUV420P;
+    int out_planes_used() const { return out_fmt == OCTVR_PIX_NV12 ? 2 : 3; }
     // preview (async.cpp:73-76): preview_w x preview_h RGB; per mapper its rectangle (w or h <= 0: none)
     int preview_w = 0, preview_h = 0;
     std::vector<Rect> preview_rects;
@@ -271,7 +283,16 @@ struct octvr_async {
     struct RegOut {
         uint8_t* p[3];
         size_t pitch[3];
+        std::vector<PinRange> pinned;  // what hipHostRegister locked: the planes' ranges, merged (merge_pin_ranges)
+        bool same(int np, uint8_t* const* planes, const size_t* pitches) const {  // pitches NULL: any
+            for (int k = 0; k < np; k++)
+                if (p[k] != planes[k] || (pitches && pitch[k] != pitches[k])) return false;
+            return true;
+        }
     };
+    static void unpin(const RegOut& r) {
+        for (const PinRange& g : r.pinned) (void)hipHostUnregister(reinterpret_cast<void*>(g.begin));
+    }
     std::vector<RegOut> reg_out;  // caller thread only (register / push / destroy)
     hipStream_t up = nullptr, comp = nullptr, down = nullptr;
     Channel<std::shared_ptr<Job>> q_in, q_up, q_map, q_down, q_out, q_done;
@@ -287,8 +308,7 @@ struct octvr_async {
         int prev = -1;
         (void)hipGetDevice(&prev);
         (void)hipSetDevice(device);
-        for (const RegOut& r : reg_out)
-            for (uint8_t* p : r.p) (void)hipHostUnregister(p);
+        for (const RegOut& r : reg_out) unpin(r);
         for (hipStream_t s : {up, comp, down})
             if (s) (void)hipStreamDestroy(s);
         for (auto& sl : slots) {
@@ -315,15 +335,9 @@ struct octvr_async {
             copy_in_pool.run(runs.size(), [&](size_t lo, size_t hi) {
                 for (size_t k = lo; k < hi; k++) {
                     const FootRun& r = runs[k];
-                    const int i = (int)(r.cam & 31u), rp = (int)(r.cam >> 8), w = in_w[i];
-                    const int x0 = 8 * (int)r.g0, yb = std::min(8 * (int)(r.g0 + r.ng), w) - x0;
-                    const int c0 = 4 * (int)r.g0, cb = std::max(0, std::min(4 * (int)(r.g0 + r.ng), w / 2) - c0);
-                    const size_t py = j.in_pitches[3 * i], pu = j.in_pitches[3 * i + 1], pv = j.in_pitches[3 * i + 2];
-                    uint8_t* d = dst + r.off;
-                    memcpy(d, j.in_planes[3 * i] + (size_t)(2 * rp) * py + x0, yb);
-                    memcpy(d + yb, j.in_planes[3 * i] + (size_t)(2 * rp + 1) * py + x0, yb);
-                    memcpy(d + 2 * yb, j.in_planes[3 * i + 1] + (size_t)rp * pu + c0, cb);
-                    memcpy(d + 2 * yb + cb, j.in_planes[3 * i + 2] + (size_t)rp * pv + c0, cb);
+                    const int i = (int)(r.cam & 31u);
+                    pack_run(dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng, &j.in_planes[3 * i],
+                             &j.in_pitches[3 * i], in_fmt == OCTVR_PIX_NV12);
                 }
             });
         });
@@ -337,7 +351,8 @@ struct octvr_async {
             Slot& sl = slots[j.slot];
             if (packed_bytes) {
                 HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, packed_bytes, hipMemcpyHostToDevice, up));
-                HIP_CHECK(launch_unpack_runs(sl.packed_dev.p, runs_dev.p, (int)runs.size(), sl.frames, up));
+                HIP_CHECK(launch_unpack_runs_layout(sl.packed_dev.p, runs_dev.p, (int)runs.size(), sl.frames,
+                                                    in_fmt == OCTVR_PIX_NV12, up));
             }
             HIP_CHECK(hipStreamSynchronize(up));
         });
@@ -392,6 +407,12 @@ struct octvr_async {
                 const uint8_t* src = sl.out_dev[k].p;
                 HIP_CHECK(hipMemcpy2DAsync(j.out_planes[0] + (size_t)r.y * j.out_pitches[0] + r.x, j.out_pitches[0], src,
                                            (size_t)r.w, (size_t)r.w, (size_t)r.h, hipMemcpyDeviceToHost, down));
+                if (out_fmt == OCTVR_PIX_NV12) {  // "Y over U,V pairs": whole chroma rows to byte column 2 c.x
+                    HIP_CHECK(hipMemcpy2DAsync(j.out_planes[1] + (size_t)c.y * j.out_pitches[1] + 2 * (size_t)c.x,
+                                               j.out_pitches[1], src + (size_t)r.h * r.w, (size_t)r.w, (size_t)r.w,
+                                               (size_t)c.h, hipMemcpyDeviceToHost, down));
+                    continue;
+                }
                 HIP_CHECK(hipMemcpy2DAsync(j.out_planes[1] + (size_t)c.y * j.out_pitches[1] + c.x, j.out_pitches[1],
                                            src + (size_t)r.h * r.w, (size_t)r.w, (size_t)c.w, (size_t)c.h,
                                            hipMemcpyDeviceToHost, down));
@@ -422,6 +443,11 @@ struct octvr_async {
                         } else {
                             const size_t cy = y - (size_t)r.h;
                             const uint8_t* row = src + (size_t)(r.h + (int)cy) * r.w;
+                            if (out_fmt == OCTVR_PIX_NV12) {
+                                memcpy(j.out_planes[1] + (size_t)(c.y + (int)cy) * j.out_pitches[1] + 2 * (size_t)c.x, row,
+                                       r.w);
+                                continue;
+                            }
                             memcpy(j.out_planes[1] + (size_t)(c.y + (int)cy) * j.out_pitches[1] + c.x, row, c.w);
                             memcpy(j.out_planes[2] + (size_t)(c.y + (int)cy) * j.out_pitches[2] + c.x, row + r.w / 2, c.w);
                         }
@@ -488,6 +514,19 @@ struct octvr_async {
         });
     }
 };
+
+namespace {
+
+// The planes the output format uses (planar: Y, U, V; NV12: Y and the U,V plane of out_w bytes per row) are
+// there and wide enough; with NV12 the third entry is ignored.
+bool output_planes_ok(const octvr_async* a, uint8_t* const* planes, const size_t* pitches) {
+    const bool nv12 = a->out_fmt == OCTVR_PIX_NV12;
+    for (int k = 0; k < a->out_planes_used(); k++)
+        if (!planes[k] || pitches[k] < (size_t)(k && !nv12 ? a->out_w / 2 : a->out_w)) return false;
+    return true;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -608,23 +647,27 @@ int octvr_async_push(octvr_async* a, const uint8_t* const* in_planes, const size
     auto j = std::make_shared<Job>();
     j->in_planes.assign(in_planes, in_planes + 3 * a->n_in);
     j->in_pitches.assign(in_pitches, in_pitches + 3 * a->n_in);
-    for (int i = 0; i < a->n_in; i++)
-        if (!in_planes[3 * i] || !in_planes[3 * i + 1] || !in_planes[3 * i + 2] || in_pitches[3 * i] < (size_t)a->in_w[i] ||
-            in_pitches[3 * i + 1] < (size_t)a->in_w[i] / 2 || in_pitches[3 * i + 2] < (size_t)a->in_w[i] / 2) {
+    for (int i = 0; i < a->n_in; i++) {
+        const size_t w = (size_t)a->in_w[i];
+        const bool bad = a->in_fmt == OCTVR_PIX_NV12
+                             ? !in_planes[3 * i] || !in_planes[3 * i + 1] || in_pitches[3 * i] < w || in_pitches[3 * i + 1] < w
+                             : !in_planes[3 * i] || !in_planes[3 * i + 1] || !in_planes[3 * i + 2] || in_pitches[3 * i] < w ||
+                                   in_pitches[3 * i + 1] < w / 2 || in_pitches[3 * i + 2] < w / 2;
+        if (bad) {
             set_last_error("bad input plane");
             return OCTVR_E_INVALID;
         }
-    for (int k = 0; k < 3; k++) {
+    }
+    if (!output_planes_ok(a, out_planes, out_pitches)) {
+        set_last_error("bad output plane");
+        return OCTVR_E_INVALID;
+    }
+    const int np = a->out_planes_used();
+    for (int k = 0; k < np; k++) {
         j->out_planes[k] = out_planes[k];
         j->out_pitches[k] = out_pitches[k];
-        if (!out_planes[k] || out_pitches[k] < (size_t)(k ? a->out_w / 2 : a->out_w)) {
-            set_last_error("bad output plane");
-            return OCTVR_E_INVALID;
-        }
     }
-    for (const octvr_async::RegOut& r : a->reg_out)
-        j->direct |= r.p[0] == out_planes[0] && r.p[1] == out_planes[1] && r.p[2] == out_planes[2] &&
-                     r.pitch[0] == out_pitches[0] && r.pitch[1] == out_pitches[1] && r.pitch[2] == out_pitches[2];
+    for (const octvr_async::RegOut& r : a->reg_out) j->direct |= r.same(np, out_planes, out_pitches);
     a->q_in.push(std::move(j));
     a->pending++;
     return OCTVR_OK;
@@ -659,30 +702,37 @@ int octvr_async_register_output(octvr_async* a, uint8_t* const* planes, const si
         set_last_error("NULL argument");
         return OCTVR_E_INVALID;
     }
-    for (int k = 0; k < 3; k++)
-        if (!planes[k] || pitches[k] < (size_t)(k ? a->out_w / 2 : a->out_w)) {
-            set_last_error("bad output plane");
-            return OCTVR_E_INVALID;
-        }
+    if (!output_planes_ok(a, planes, pitches)) {
+        set_last_error("bad output plane");
+        return OCTVR_E_INVALID;
+    }
+    const int np = a->out_planes_used();
     for (const octvr_async::RegOut& r : a->reg_out)
-        if (r.p[0] == planes[0] && r.p[1] == planes[1] && r.p[2] == planes[2] && r.pitch[0] == pitches[0] &&
-            r.pitch[1] == pitches[1] && r.pitch[2] == pitches[2])
-            return OCTVR_OK;  // already registered
+        if (r.same(np, planes, pitches)) return OCTVR_OK;  // already registered
     return guarded([&] {
         DeviceGuard dg(a->device);
         octvr_async::RegOut r{};
-        int done = 0;
-        for (; done < 3; done++) {
-            const size_t rows = done ? (size_t)a->out_h / 2 : (size_t)a->out_h;
-            const size_t w = done ? (size_t)a->out_w / 2 : (size_t)a->out_w;
-            const hipError_t e = hipHostRegister(planes[done], pitches[done] * (rows - 1) + w, hipHostRegisterDefault);
+        // Planes of one allocation (a contiguous NV12 frame's Y and U,V; U and V as column halves of one
+        // array) share pages or overlap: each page is locked once, through the merged range that holds it
+        std::vector<PinRange> ranges;
+        const bool nv12 = a->out_fmt == OCTVR_PIX_NV12;
+        for (int k = 0; k < np; k++) {
+            const size_t rows = k ? (size_t)a->out_h / 2 : (size_t)a->out_h;
+            const size_t w = k && !nv12 ? (size_t)a->out_w / 2 : (size_t)a->out_w;
+            const uintptr_t b = reinterpret_cast<uintptr_t>(planes[k]);
+            ranges.push_back(PinRange{b, b + pitches[k] * (rows - 1) + w});
+            r.p[k] = planes[k];
+            r.pitch[k] = pitches[k];
+        }
+        const long page = sysconf(_SC_PAGESIZE);
+        for (const PinRange& g : merge_pin_ranges(ranges, (uintptr_t)(page > 0 ? page : 4096))) {
+            const hipError_t e = hipHostRegister(reinterpret_cast<void*>(g.begin), g.end - g.begin, hipHostRegisterDefault);
             if (e != hipSuccess) {
-                for (int k = 0; k < done; k++) (void)hipHostUnregister(planes[k]);
+                octvr_async::unpin(r);
                 (void)hipGetLastError();
                 throw OctvrError(OCTVR_E_HIP, std::string("hipHostRegister: ") + hipGetErrorString(e));
             }
-            r.p[done] = planes[done];
-            r.pitch[done] = pitches[done];
+            r.pinned.push_back(g);
         }
         a->reg_out.push_back(r);
     }, OCTVR_E_HIP);
@@ -699,14 +749,51 @@ int octvr_async_unregister_output(octvr_async* a, uint8_t* const* planes) {
     }
     for (size_t i = 0; i < a->reg_out.size(); i++) {
         const octvr_async::RegOut& r = a->reg_out[i];
-        if (r.p[0] != planes[0] || r.p[1] != planes[1] || r.p[2] != planes[2]) continue;
+        if (!r.same(a->out_planes_used(), planes, nullptr)) continue;
         DeviceGuard dg(a->device);
-        for (uint8_t* p : r.p) (void)hipHostUnregister(p);
+        octvr_async::unpin(r);
         a->reg_out.erase(a->reg_out.begin() + (long)i);
         return OCTVR_OK;
     }
     set_last_error("planes not registered");
     return OCTVR_E_INVALID;
+}
+
+int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format) {
+    return guarded([&] {
+        REQUIRE(a, "NULL argument");
+        REQUIRE((in_format == OCTVR_PIX_YUV420P || in_format == OCTVR_PIX_NV12) &&
+                    (out_format == OCTVR_PIX_YUV420P || out_format == OCTVR_PIX_NV12),
+                "pixel format must be OCTVR_PIX_YUV420P or OCTVR_PIX_NV12");
+        REQUIRE(a->pending == 0, "frames pending: pop them before changing the pixel formats");
+        REQUIRE(out_format == a->out_fmt || a->reg_out.empty(),
+                "output planes are registered: unregister them before changing the output format");
+        // the footprint runs are shared by both layouts because a run's NV12 chroma row is as long as its
+        // U and V rows together, which needs even widths (they are, since creation)
+        for (int w : a->in_w) REQUIRE(w % 2 == 0, "input widths must be even");
+        for (octvr_mapper* m : a->mappers) {
+            const int rc = octvr_mapper_set_pixel_formats(m, in_format, out_format);
+            if (rc != OCTVR_OK) throw OctvrError(rc, octvr_last_error());
+        }
+        if (in_format != a->in_fmt) {  // the other layout's chroma cells are elsewhere: back to the pattern
+            DeviceGuard dg(a->device);
+            for (auto& sl : a->slots)
+                for (int i = 0; i < a->n_in; i++)
+                    HIP_CHECK(hipMemset(sl.in_dev[i].p, 0x5A, (size_t)a->in_w[i] * (a->in_h[i] / 2 * 3)));
+        }
+        a->in_fmt = in_format;
+        a->out_fmt = out_format;
+    }, OCTVR_E_HIP);
+}
+
+int octvr_async_pixel_formats(const octvr_async* a, int* in_format, int* out_format) {
+    if (!a || !in_format || !out_format) {
+        set_last_error("NULL argument");
+        return OCTVR_E_INVALID;
+    }
+    *in_format = a->in_fmt;
+    *out_format = a->out_fmt;
+    return OCTVR_OK;
 }
 
 int octvr_async_pop_preview(octvr_async* a, uint8_t* rgb, size_t pitch, octvr_preview_header* hdr) {
@@ -745,12 +832,12 @@ int octvr_async_info(const octvr_async* a, char* buf, size_t len) {
     size_t in_bytes = 0, out_bytes = 0;
     for (int i = 0; i < a->n_in; i++) in_bytes += (size_t)a->in_w[i] * (a->in_h[i] / 2 * 3);
     for (const Rect& r : a->regions) out_bytes += (size_t)r.w * (r.h / 2 * 3);
-    char tmp[512];
+    char tmp[640];
     snprintf(tmp, sizeof tmp,
              "{\"mappers\": %d, \"inputs\": %d, \"packed_bytes\": %zu, \"runs\": %zu, \"input_frame_bytes\": %zu, "
-             "\"output_bytes\": %zu, \"preview\": [%d, %d], \"flags\": %d, \"slots\": %d}",
+             "\"output_bytes\": %zu, \"preview\": [%d, %d], \"flags\": %d, \"slots\": %d, \"pixel_formats\": [%d, %d]}",
              (int)a->mappers.size(), a->n_in, a->packed_bytes, a->runs.size(), in_bytes, out_bytes, a->preview_w,
-             a->preview_h, a->flags, kSlots);
+             a->preview_h, a->flags, kSlots, a->in_fmt, a->out_fmt);
     if (strlen(tmp) >= len) {
         set_last_error("buffer too small");
         return OCTVR_E_INVALID;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "abi_guard.hpp"
+#include "async_host.hpp"
 #include "camera_math.hpp"
 #include "json_lite.hpp"
 #include "mapper.hpp"
@@ -16,6 +17,42 @@
 using namespace octvr;
 
 extern "C" {
+
+int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const uint32_t* runs, int n_runs,
+                          const uint8_t* const* planes, const size_t* pitches, int format, uint8_t* packed, size_t cap,
+                          size_t* sizes, size_t* bytes) {
+    return guarded([&] {
+        REQUIRE(in_w && in_h && runs && planes && pitches && packed && bytes, "NULL argument");
+        REQUIRE(n_inputs > 0 && n_inputs <= kMaxCams && n_runs >= 0, "bad counts");
+        REQUIRE(format == OCTVR_PIX_YUV420P || format == OCTVR_PIX_NV12,
+                "pixel format must be OCTVR_PIX_YUV420P or OCTVR_PIX_NV12");
+        const bool nv12 = format == OCTVR_PIX_NV12;
+        for (int i = 0; i < n_inputs; i++) {
+            const size_t w = (size_t)in_w[i];
+            REQUIRE(in_w[i] > 0 && in_h[i] > 0 && in_w[i] % 2 == 0 && in_h[i] % 2 == 0, "input sizes must be even");
+            REQUIRE(planes[3 * i] && planes[3 * i + 1] && pitches[3 * i] >= w, "bad input plane");
+            if (nv12)
+                REQUIRE(pitches[3 * i + 1] >= w, "bad input plane");
+            else
+                REQUIRE(planes[3 * i + 2] && pitches[3 * i + 1] >= w / 2 && pitches[3 * i + 2] >= w / 2, "bad input plane");
+        }
+        size_t off = 0;
+        for (int k = 0; k < n_runs; k++) {
+            const uint32_t cam = runs[4 * k], rp = runs[4 * k + 1], g0 = runs[4 * k + 2], ng = runs[4 * k + 3];
+            REQUIRE(cam < (uint32_t)n_inputs, "run: no such camera");
+            const int w = in_w[cam], h = in_h[cam];
+            REQUIRE(rp < (uint32_t)h / 2 && ng > 0 && g0 < (uint32_t)(w + 7) / 8 && ng <= (uint32_t)(w + 7) / 8 - g0,
+                    "run outside its frame");
+            const size_t n = 3 * (size_t)run_luma_bytes(w, (int)g0, (int)ng);
+            REQUIRE(off + n <= cap, "buffer too small");
+            const size_t got = pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam, nv12);
+            REQUIRE(got == n, "pack_run size");
+            if (sizes) sizes[k] = got;
+            off += got;
+        }
+        *bytes = off;
+    });
+}
 
 int octvr_debug_gain_plan(const octvr_rig* rig, int n_inputs, const int* in_w, const int* in_h, int flags,
                           uint32_t* samples, uint16_t* partners, size_t cap, size_t* count) {

@@ -279,6 +279,11 @@ struct FootFrames {
 };
 hipError_t launch_unpack_runs(const uint8_t* packed, const FootRun* runs, int n_runs, const FootFrames& frames,
                               hipStream_t s);
+// The same for a pipeline whose input frames are NV12 (async_kernels.hip): the run's chroma is one row of
+// 8 ng bytes of U,V pairs (cut at the width) at byte column 8 g0, the frames "Y over U,V pairs"; nv12 == 0 is
+// launch_unpack_runs.
+hipError_t launch_unpack_runs_layout(const uint8_t* packed, const FootRun* runs, int n_runs, const FootFrames& frames,
+                                     int nv12, hipStream_t s);
 
 struct TiledLut {
     const TileHdr* meta;          // per staged item kMetaWords 16-byte words: the TileHdr, then kTileSlots TileSlots

@@ -122,6 +122,9 @@ _lib.octvr_async_unregister_output.argtypes = [_VP, C.POINTER(_VP)]
 _lib.octvr_async_push.argtypes = [_VP, C.POINTER(_VP), C.POINTER(C.c_size_t), C.POINTER(_VP), C.POINTER(C.c_size_t)]
 _lib.octvr_async_pop.argtypes = [_VP]
 _lib.octvr_async_pending.argtypes = [_VP, C.POINTER(C.c_int)]
+if hasattr(_lib, "octvr_async_set_pixel_formats"):  # (absent from older libraries OCTVR_HIP_LIB may select for an A/B)
+    _lib.octvr_async_set_pixel_formats.argtypes = [_VP, C.c_int, C.c_int]
+    _lib.octvr_async_pixel_formats.argtypes = [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 _lib.octvr_async_destroy.argtypes = [_VP]
 _lib.octvr_async_destroy.restype = None
 _lib.octvr_fill_poly_u8.argtypes = [_VP, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_uint8]
@@ -146,6 +149,9 @@ if hasattr(_lib, "octvr_debug_fastmapper_audit"):
 if hasattr(_lib, "octvr_debug_gain_plan"):
     _lib.octvr_debug_gain_plan.argtypes = [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _VP, _VP,
                                            C.c_size_t, C.POINTER(C.c_size_t)]
+if hasattr(_lib, "octvr_debug_pack_runs"):
+    _lib.octvr_debug_pack_runs.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _VP, C.c_int, C.POINTER(_VP),
+                                           C.POINTER(C.c_size_t), C.c_int, _VP, C.c_size_t, _VP, C.POINTER(C.c_size_t)]
 if hasattr(_lib, "octvr_debug_worker_failure"):
     _lib.octvr_debug_worker_failure.argtypes = [C.c_int, C.c_int]
 _lib.octvr_remap_u8.argtypes = [_VP, C.c_int, C.c_int, C.c_size_t, C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_size_t,
@@ -184,6 +190,44 @@ def debug_tiled_lut_info(mt, in_sizes, remap="remap"):
     _check(_lib.octvr_debug_tiled_lut_info(mt._h, n, w, h, REMAP_TEXTURE if remap == "texture" else 0, buf, len(buf)))
     import json as _json
     return _json.loads(buf.value.decode())
+
+
+def _plane_args(plane_sets):
+    """(pointers, pitches, kept arrays) of (Y, U, V) or (Y, UV[, None]) plane tuples, three entries per set; a
+    missing or None third plane is a NULL pointer with pitch 0 (NV12: octvr_async_set_pixel_formats)."""
+    planes = []
+    for tri in plane_sets:
+        tri = list(tri)
+        if len(tri) not in (2, 3):
+            raise ValueError("a plane set is (Y, U, V), or (Y, UV) for an NV12 side")
+        tri += [None] * (3 - len(tri))
+        for p in tri:
+            if p is not None:
+                assert p.dtype == np.uint8 and p.ndim == 2 and p.strides[1] == 1, \
+                    "uint8 2-D planes with unit column stride"
+            planes.append(p)
+    ptr = (_VP * len(planes))(*[None if p is None else p.ctypes.data for p in planes])
+    pitch = (C.c_size_t * len(planes))(*[0 if p is None else p.strides[0] for p in planes])
+    return ptr, pitch, planes
+
+
+def debug_pack_runs(in_sizes, runs, planes, fmt="yuv420p"):
+    """(packed, sizes): the AsyncMultiMapper copy-in's packing (octvr_debug_pack_runs; no GPU) of `runs`, rows
+    of (camera, row pair, first group, groups), from per-camera plane tuples laid out as push() takes them
+    for `fmt` — the packed bytes back to back and each run's size."""
+    n = len(in_sizes)
+    w = (C.c_int * n)(*[s[0] for s in in_sizes])
+    h = (C.c_int * n)(*[s[1] for s in in_sizes])
+    r = np.ascontiguousarray(np.asarray(runs, np.uint32).reshape(-1, 4))
+    ptr, pitch, keep = _plane_args(planes)
+    cap = int(sum(3 * 8 * int(x[3]) for x in r)) + 8
+    packed = np.full(cap, 0x5A, np.uint8)
+    sizes = np.zeros(len(r), np.uintp)
+    total = C.c_size_t()
+    _check(_lib.octvr_debug_pack_runs(n, w, h, r.ctypes.data_as(_VP), len(r), ptr, pitch, _pix_value(fmt),
+                                      packed.ctypes.data_as(_VP), cap, sizes.ctypes.data_as(_VP), C.byref(total)))
+    assert (packed[total.value:] == 0x5A).all()
+    return packed[:total.value].copy(), sizes.astype(np.int64)
 
 
 def debug_worker_failure(n_threads, failing):
@@ -653,7 +697,8 @@ class FastMapper:
 
 class AsyncMultiMapper:
     """vr::AsyncMultiMapper (modules/octvr/src/async.cpp): host YUV420P planes in, host planes out, through
-    a 3-deep pinned-buffer pipeline (copy-in, H2D, stitch, D2H, copy-out overlap across frames).
+    a 3-deep pinned-buffer pipeline (copy-in, H2D, stitch, D2H, copy-out overlap across frames).  Either side
+    may be NV12 instead (set_pixel_formats): its plane sets are then (Y, UV) two-tuples.
 
     templates: list of MapperTemplate (all with the same inputs); output_regions: list of (x, y, w, h)
     fractions of out_size; gain_modes[i]: -1 no gain, i estimate, j < i reuse mapper j's gains.
@@ -694,14 +739,11 @@ class AsyncMultiMapper:
 
     def push(self, inputs, output):
         """inputs: list of (Y, U, V) uint8 numpy planes per camera; output: (Y, U, V) planes of the merged
-        frame.  The arrays are kept alive until the matching pop()."""
-        planes = [p if p.strides[1] == 1 else np.ascontiguousarray(p) for tri in inputs for p in tri]
-        for p in list(planes) + list(output):
-            assert p.dtype == np.uint8 and p.ndim == 2 and p.strides[1] == 1, "uint8 2-D planes with unit column stride"
-        ip = (_VP * len(planes))(*[p.ctypes.data for p in planes])
-        ipt = (C.c_size_t * len(planes))(*[p.strides[0] for p in planes])
-        op = (_VP * 3)(*[p.ctypes.data for p in output])
-        opt = (C.c_size_t * 3)(*[p.strides[0] for p in output])
+        frame; a side that is NV12 takes (Y, UV) — UV the interleaved plane of W bytes x H/2 rows — with an
+        optional third entry that is ignored.  The arrays are kept alive until the matching pop()."""
+        fix = lambda p: p if p is None or p.strides[1] == 1 else np.ascontiguousarray(p)
+        ip, ipt, planes = _plane_args([tuple(fix(p) for p in tri) for tri in inputs])
+        op, opt, _ = _plane_args([output])
         _check(_lib.octvr_async_push(self._h, ip, ipt, op, opt))
         self._inflight.append((planes, output))
 
@@ -718,19 +760,31 @@ class AsyncMultiMapper:
         return n.value
 
     def register_output(self, output):
-        """Page-lock an output (Y, U, V) plane set the caller will push again (octvr_async_register_output): its
-        frames are then downloaded straight into it.  The arrays are kept alive until close()."""
-        for p in output:
-            assert p.dtype == np.uint8 and p.ndim == 2 and p.strides[1] == 1
-        op = (_VP * 3)(*[p.ctypes.data for p in output])
-        opt = (C.c_size_t * 3)(*[p.strides[0] for p in output])
+        """Page-lock an output (Y, U, V) plane set — (Y, UV) with an NV12 output — the caller will push again
+        (octvr_async_register_output): its frames are then downloaded straight into it.  Planes that are
+        views of one array (a contiguous NV12 frame's a[:H] and a[H:]) are locked as one range.  The arrays are
+        kept alive until close()."""
+        op, opt, _ = _plane_args([output])
         _check(_lib.octvr_async_register_output(self._h, op, opt))
         self._registered.append(tuple(output))
 
     def unregister_output(self, output):
-        op = (_VP * 3)(*[p.ctypes.data for p in output])
+        op, _, _ = _plane_args([output])
         _check(_lib.octvr_async_unregister_output(self._h, op))
-        self._registered = [r for r in self._registered if not all(a is b for a, b in zip(r, output))]
+        self._registered = [r for r in self._registered
+                            if not (len(r) == len(output) and all(a is b for a, b in zip(r, output)))]
+
+    def set_pixel_formats(self, in_format="yuv420p", out_format="yuv420p"):
+        """Layouts of the host planes of every later push, "yuv420p" (the default) or "nv12", or the
+        OCTVR_PIX_* values (octvr_async_set_pixel_formats): no frame may be pending, and the output format
+        cannot change while output plane sets are registered."""
+        _check(_lib.octvr_async_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
+
+    @property
+    def pixel_formats(self):
+        a, b = C.c_int(), C.c_int()
+        _check(_lib.octvr_async_pixel_formats(self._h, C.byref(a), C.byref(b)))
+        return PIX_NAMES[a.value], PIX_NAMES[b.value]
 
     def preview(self):
         """(rgb, header): the latest published preview as an (h, w, 3) uint8 array and its PreviewDataHeader
