@@ -460,6 +460,11 @@ public:
     // blend: 0 = do not blend, > 0 = multi-band blend width, < 0 = feather blend width.
     // flags (not in the reference): OCTVR_REMAP_TEXTURE samples as the reference's CUDA fastRemap does
     // (octvr_hip.h octvr_mapper_create_ex); 0 = cv::remap's fixed point.
+    // in_sizes: one per input, then one per overlay of mt (mapper.cpp:208: inputs.size() == masks.size());
+    // stitch takes the frames in the same order.  The overlays' frames are warped like the inputs, never
+    // gained or blended, and copied onto the blended result where their mask is set (mapper.cpp:279-287; the
+    // reference omits their RGBA -> RGB conversion there and fails in copyTo: parity unpinned, the behaviour is
+    // the reference's with that conversion restored).
     Mapper(const MapperTemplate& mt, std::vector<cv::Size> in_sizes, int blend = 128,
            bool enable_gain_compensator = true, cv::Size scale_output = cv::Size(0, 0), int flags = 0) {
         rig_ = mt.rig();
@@ -469,6 +474,7 @@ public:
             h.push_back(s.height);
         }
         n_ = (int)in_sizes.size();
+        n_gains_ = n_ - (int)mt.overlay_inputs.size();
         octvr_mapper* m = nullptr;
         detail::check(octvr_mapper_create_ex(rig_.get(), detail::device(), n_, w.data(), h.data(), blend,
                                              enable_gain_compensator ? 1 : 0, scale_output.width, scale_output.height,
@@ -508,8 +514,8 @@ public:
         detail::check(octvr_stream_sync(nullptr));
     }
     std::vector<double> gains() const {
-        std::vector<double> g(n_);
-        detail::check(octvr_mapper_gains(m_.get(), g.data(), n_));
+        std::vector<double> g(n_gains_);  // one per input; overlays have none
+        detail::check(octvr_mapper_gains(m_.get(), g.data(), n_gains_));
         return g;
     }
     // Pixel layouts of the inputs (all alike) and of the output of every later stitch (no reference
@@ -529,7 +535,7 @@ public:
 private:
     detail::RigPtr rig_;
     std::shared_ptr<octvr_mapper> m_;
-    int n_ = 0;
+    int n_ = 0, n_gains_ = 0;
     cv::Size out_;
     std::vector<cv::Size> sizes_;
 };
@@ -542,7 +548,9 @@ struct PreviewDataHeader {
 static_assert(sizeof(PreviewDataHeader) == sizeof(octvr_preview_header), "PreviewDataHeader = octvr_preview_header");
 
 // AsyncMultiMapper (octvr.hpp:103-121, async.cpp:195-350): several mappers over the same frames, each
-// writing its region of one merged output, behind a 3-deep H2D / stitch / D2H pipeline.
+// writing its region of one merged output, behind a 3-deep H2D / stitch / D2H pipeline.  in_sizes and the
+// frames of push() cover every template's inputs and then its overlays, as each Mapper asserts; how the
+// frames split into inputs and overlays may differ per template.
 class AsyncMultiMapper {
 public:
     static AsyncMultiMapper* New(const std::vector<MapperTemplate>& mts, std::vector<cv::Size> in_sizes,

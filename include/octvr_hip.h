@@ -140,7 +140,21 @@ int octvr_rig_clone(const octvr_rig* rig, octvr_rig** out);
  * blend: 0 = no blend (composite by LUT mask, later input wins; mapper.cpp:268-277), > 0 multi-band
  * with ceil(log2(blend)) - 1 bands (MultiBandGPUBlender), < 0 feather with border -blend
  * (FeatherGPUBlender); blend != 0 needs seam masks (octvr_rig_create_masks or a .dat).
- * scale_w/scale_h: 0 = output at template size, else the output is resized (mapper.cpp:290-306). */
+ * scale_w/scale_h: 0 = output at template size, else the output is resized (mapper.cpp:290-306).
+ * Overlays: a rig with N inputs and K overlays takes n_inputs = N + K sizes (inputs, then overlays; anything
+ * else is OCTVR_E_INVALID), N + K <= 32, and every in_dev / in_pitch array of the stitch calls below holds N + K
+ * entries per frame: camera N + k is overlay k's live frame, of its own even size, in the same layout and under
+ * the same pitch rules as the inputs (octvr_mapper_set_pixel_formats covers it).  An overlay goes through the
+ * inputs' per-pixel path (YUV -> RGB, vignette, remap in the mapper's sampling convention) but is never gained
+ * and stays out of the gain estimation and the blenders: after the blend over the N inputs, for k = 0 .. K - 1,
+ * result(roi_k)[mask_k != 0] = warped_k (a later overlay wins), and the scaled output, the RGB -> YUV420
+ * conversion and the preview are taken from the patched result (mapper.cpp:279-312).  Parity unpinned: the
+ * reference omits the overlays' RGBA -> RGB conversion before copyTo (mapper.cpp:147-151, 270) and fails there;
+ * this is its behaviour with that conversion restored.  Gains stay one per input (N): n_gains, octvr_mapper_gains.
+ * A single input disables gain and blend whatever overlays it has (mapper.cpp:78-82).  With blend 0 the overlays
+ * are the last cameras of the composite LUT (no extra pass; frames in flight and batches as usual, a batch of 4
+ * needs N + K <= 16).  With blend != 0 the mapper stitches through its one RGBA result frame, overlay_apply_kernel
+ * patches it, and the identity resize converts it: more than one frame in flight is OCTVR_E_UNSUPPORTED. */
 int octvr_mapper_create(const octvr_rig* rig, int device, int n_inputs, const int* in_w, const int* in_h, int blend,
                         int enable_gain, int scale_w, int scale_h, octvr_mapper** mapper);
 /* The same with creation flags (no reference counterpart; 0 = octvr_mapper_create).
@@ -160,17 +174,19 @@ int octvr_mapper_create_ex(const octvr_rig* rig, int device, int n_inputs, const
 /* Mapper::stitch (mapper.cpp:193-323) on device-resident YUV420P frames in the "Y over [U|V]"
  * layout of mapper.hpp:75-83: rows [0,H) = Y (W bytes), rows [H, 3H/2) = U in bytes [0, W/2) and
  * V in bytes [W/2, W) of each row; `pitch` = bytes per row (>= W).  gains: NULL = estimate
- * (GainCompensatorGPU::feed), else set_gains (n_gains == n_inputs).  Stream-ordered, no host sync. */
+ * (GainCompensatorGPU::feed), else set_gains (n_gains == the rig's inputs N, overlays aside).  Stream-ordered,
+ * no host sync. */
 int octvr_mapper_stitch_yuv420p(octvr_mapper* mapper, const uint8_t* const* in_dev, const size_t* in_pitch,
                                 uint8_t* out_dev, size_t out_pitch, const double* gains, int n_gains, void* stream);
 /* n_frames (1, 2 or 4) consecutive frames of the same rig in one call (no reference counterpart; the
  * reference stitches a frame per Mapper::stitch): frame f's inputs are in_dev[f * n_inputs + i] /
  * in_pitch[...], its output out_dev[f] (all outputs of pitch out_pitch); gains NULL = estimate every frame's
- * own gains, else n_frames * n_inputs values.  Each frame gets its own gain feed into its own frame slot, then
+ * own gains, else n_frames * N values (N: the rig's inputs without its overlays).  Each frame gets its own gain feed into its own frame slot, then
  * ONE composite launch stitches all of them: its work runs over (item, frame) pairs, so an item's LUT entries,
  * metadata and staging groups are fetched once for the batch.  Every output equals a separate stitch of its
  * frame, bit for bit.  Needs n_frames frames in flight (octvr_mapper_set_frames_in_flight) and, for 4, at
- * most 16 inputs; scaled-output and multi-band / feather mappers stitch the frames one by one. */
+ * most 16 inputs and overlays together; scaled-output and multi-band / feather mappers stitch the frames one
+ * by one. */
 int octvr_mapper_stitch_batch(octvr_mapper* mapper, int n_frames, const uint8_t* const* in_dev, const size_t* in_pitch,
                               uint8_t* const* out_dev, size_t out_pitch, const double* gains, void* stream);
 /* The same with Mapper::stitch's preview_output (mapper.cpp:308-312): the RGB result resized
@@ -179,14 +195,16 @@ int octvr_mapper_stitch_batch(octvr_mapper* mapper, int n_frames, const uint8_t*
 int octvr_mapper_stitch_preview(octvr_mapper* mapper, const uint8_t* const* in_dev, const size_t* in_pitch,
                                 uint8_t* out_dev, size_t out_pitch, uint8_t* preview_dev, int preview_w, int preview_h,
                                 size_t preview_pitch, const double* gains, int n_gains, void* stream);
-/* Mapper::gains() (mapper.hpp:88-90): gains used by the last stitch (synchronizes the stream). */
+/* Mapper::gains() (mapper.hpp:88-90): gains used by the last stitch, one per input (n >= N; overlays have
+ * none) (synchronizes the stream). */
 int octvr_mapper_gains(octvr_mapper* mapper, double* gains, int n);
 /* Frames in flight (no reference counterpart: vr::Mapper is not re-entrant, and AsyncMultiMapper
  * serialises its stitches on one compute stream, async.cpp:78-92).  k slots of per-frame device state
  * (gains, gain-feed totals, composite work queue); consecutive stitches take the slots in turn, so
  * stitches issued on different streams overlap (frame k+1's gain feed under frame k's composite).
  * A stitch waits (through an event) only for its slot's previous stitch.
- * k > 1 needs the output at template size (no scaled output; OCTVR_E_UNSUPPORTED otherwise);
+ * k > 1 needs the output at template size (no scaled output; OCTVR_E_UNSUPPORTED otherwise) and, on a
+ * multi-band / feather mapper, no overlays (they are copied onto the one result frame; OCTVR_E_UNSUPPORTED);
  * multi-band / feather mappers get per-slot pyramids.  Synchronizes. */
 #define OCTVR_MAX_FRAMES_IN_FLIGHT 16
 int octvr_mapper_set_frames_in_flight(octvr_mapper* mapper, int k);
@@ -208,7 +226,9 @@ int octvr_mapper_set_pixel_formats(octvr_mapper* mapper, int in_format, int out_
 int octvr_mapper_pixel_formats(const octvr_mapper* mapper, int* in_format, int* out_format);
 /* Algorithmic device bytes read+written by one launch of the composite (stitch) kernel: 4 B tiled
  * LUT entry (8 B in wide tiles) + 1.5 B YUV420 out per output pixel + 1.5 B per input pixel (each
- * source frame read once) + the per-item headers (multi-band / feather: the whole blend sequence). */
+ * source frame read once) + the per-item headers (multi-band / feather: the whole blend sequence; with
+ * overlays also the result frame's read-back, overlay_apply_kernel's work list, the source bytes under its taps
+ * and the pixels it writes). */
 int octvr_mapper_traffic(const octvr_mapper* mapper, double* bytes_per_frame);
 /* The same split into the rig constants the composite reads once per launch (tiled-LUT entries, item headers,
  * wide-tile entries: read once for a whole frame batch, octvr_mapper_stitch_batch) and the per-frame bytes
@@ -230,7 +250,9 @@ int octvr_mapper_kernel_intervals(octvr_mapper* mapper, double* start_ms, double
 /* The arithmetic behind kernel_busy, on host arrays: span = sum of (end - start), busy = length of the
  * union of the n intervals [start[k], end[k]] (overlapping, nested, touching or disjoint, any order). */
 int octvr_interval_union(const double* start, const double* end, int n, double* span, double* busy);
-/* Build-time statistics of a mapper as a JSON object (tiles, wide tiles, staged bytes, gain samples). */
+/* Build-time statistics of a mapper as a JSON object (tiles, wide tiles, staged bytes, gain samples;
+ * "inputs": N, "overlays": K, and for a multi-band / feather mapper overlay_apply_kernel's "overlay_groups" and
+ * "overlay_px"). */
 int octvr_mapper_info(const octvr_mapper* mapper, char* buf, size_t len);
 void octvr_mapper_destroy(octvr_mapper* mapper);
 
@@ -239,7 +261,9 @@ void octvr_mapper_destroy(octvr_mapper* mapper);
  * (modules/octvr/src/async.cpp:195-350, octvr.hpp:103-121): one vr::Mapper per rig, all fed the same
  * n_inputs camera frames, each writing the region output_regions[4*i .. 4*i+3] = (x, y, w, h) (fractions
  * of out_w x out_h, async.cpp:20-30) of one merged YUV420P output.  gain_modes[i]: -1 = no gain, i = estimate,
- * j in [0, i) = use mapper j's gains of the same frame (async.cpp:78-86).  A 3-deep pipeline of pinned host
+ * j in [0, i) = use mapper j's gains of the same frame (async.cpp:78-86; rigs i and j then have the same number
+ * of inputs, else OCTVR_E_INVALID).  n_inputs = N_i + K_i for every rig i (inputs, then overlays, as each
+ * reference Mapper asserts against the shared frames); the split may differ per rig.  A 3-deep pipeline of pinned host
  * and device buffers overlaps the host copies, the H2D upload, the stitch and the D2H download of
  * consecutive frames (async.cpp:32-172).  No preview: octvr_async_create_preview adds it. */
 typedef struct octvr_async octvr_async;

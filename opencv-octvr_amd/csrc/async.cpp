@@ -590,7 +590,11 @@ int octvr_async_create_preview(const octvr_rig* const* rigs, int n_rigs, int dev
                                                   gain_modes[k] >= 0 ? 1 : 0, r.w, r.h, flags, &m);
             if (rc != OCTVR_OK) throw OctvrError(rc, std::string("mapper ") + std::to_string(k) + ": " + octvr_last_error());
             a->mappers.push_back(m);
-            REQUIRE(mapper_num_inputs(m) == n_inputs, "every rig must have n_inputs inputs (no overlays)");
+            // n_inputs = N_k + K_k held for this rig (mapper_create); the split may differ per rig, but a
+            // chained mapper takes the other's N gains
+            const int gm = gain_modes[k];
+            REQUIRE(gm < 0 || gm >= k || mapper_num_inputs(a->mappers[gm]) == mapper_num_inputs(m),
+                    "gain_modes chains rigs with different numbers of inputs (overlays aside)");
         }
         DeviceGuard dg(device);
         HIP_CHECK(hipStreamCreateWithFlags(&a->up, hipStreamNonBlocking));

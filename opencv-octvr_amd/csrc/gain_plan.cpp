@@ -88,10 +88,18 @@ GainPlan plan_gain(const octvr_rig& rig, int n, const std::vector<int>& in_w, co
             for (int x = 0; x < ww; x++) {
                 int sx = (int)(x * fx), sy = (int)(y * fy);
                 size_t k = (size_t)sy * in.roi[2] + sx;
-                CompositeEntry e{0, 0};
-                if (in.mask[k])
-                    e = tex ? make_entry_tex(in.map1[k], in.map2[k], (float)in_w[i], (float)in_h[i], i)
-                            : make_entry(in.map1[k], in.map2[k], (float)in_w[i], (float)in_h[i], i);
+                // The feed reads the warped image, which the remap fills whatever the LUT mask says: a pixel
+                // whose mask an include mask of another camera or of an overlay cleared (template.cpp:102-116)
+                // still carries its in-image map value, and the linearly resized mask can be non-zero there.
+                // Mask-0 pixels whose taps all lie outside the image stay zero samples: their taps read 0 either
+                // way, so the sums are the same; this only keeps the sample order and the footprint of rigs
+                // without cleared masks as they were.
+                CompositeEntry e = tex ? make_entry_tex(in.map1[k], in.map2[k], (float)in_w[i], (float)in_h[i], i)
+                                       : make_entry(in.map1[k], in.map2[k], (float)in_w[i], (float)in_h[i], i);
+                if (!in.mask[k] && !tex) {
+                    const TapCell c = tap_cell(e.xy, in_w[i], in_h[i]);
+                    if (!((c.ix0 || c.ix1) && (c.iy0 || c.iy1))) e = CompositeEntry{0, 0};
+                }
                 samp[i][(size_t)y * ww + x] = e;
             }
         int nz = 0;

@@ -243,6 +243,15 @@ struct SourceFootprint {
 };
 void footprint_add_tiles(SourceFootprint& f, const TiledLutBuild& b);
 
+// ---- overlays of a multi-band / feather mapper: overlay_apply_kernel's work list on the device (mapper.cpp) ----
+struct OverlayListDev {
+    DevBuf<uint32_t> groups;
+    DevBuf<CompositeEntry> entries;
+    size_t covered = 0;       // pixels the overlays write
+    double source_bytes = 0;  // unique YUV bytes under their taps
+    OverlayList view{};
+};
+
 // ---- multi-band blend (multiband_host.cpp) ---------------------------------------------------------
 class MultiBand;
 struct MultiBandDeleter {

@@ -540,6 +540,26 @@ hipError_t launch_resize_rgba_yuv420(const uint8_t* rgba, int sw, int sh, int64_
 hipError_t launch_resize_rgba_rgb(const uint8_t* rgba, int sw, int sh, int64_t spitch, uint8_t* out, int dw, int dh,
                                   int64_t out_pitch, hipStream_t s);
 
+// ---- overlays after a blend (overlay.hip) -------------------------------------------------------
+// A multi-band / feather mapper copies its overlays onto the RGBA result frame after the blend:
+// result(roi_k)[mask_k != 0] = warped_k for k = 0 .. K - 1 (mapper.cpp:279-287 with the missing RGBA2RGB
+// restored).  The winner among the overlays is resolved once per rig (composite_lut_kernel over the
+// overlay templates), and only the 8-pixel groups (8 g <= x < 8 g + 8 of one row) that hold a covered pixel
+// are kept, in row-major order: per group its position and 8 entries.  A covered pixel carries
+// kCodeCovered — also where the entry is invalid (a texture-convention coordinate outside the plane), which
+// is written black like any other covered pixel; entries without it are neither read nor written.
+constexpr uint32_t kCodeCovered = 1u << 29;
+constexpr int kOvGroupPx = 8;
+constexpr int kOvBlockGroups = 256 / kOvGroupPx;  // groups of one workgroup (8 per wave)
+struct OverlayList {
+    const uint32_t* groups;         // x / 8 | y << 16
+    const CompositeEntry* entries;  // kOvGroupPx per group; camera = the overlay's frame index N + k
+    int n_groups;                   // a multiple of kOvBlockGroups (padded with uncovered groups at (0, 0))
+};
+// rgba: the W x H result frame, 4 bytes per pixel; every covered pixel lies inside it (overlay_list.cpp)
+hipError_t launch_overlay_apply(const FrameSet& frames, const OverlayList& list, uint8_t* rgba, int64_t rgba_pitch,
+                                hipStream_t s, int pix = 0);
+
 hipError_t launch_selftest_sat(const float* in, uint8_t* out, int n, int method, hipStream_t s);
 
 }  // namespace octvr

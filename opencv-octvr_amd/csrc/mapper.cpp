@@ -1,6 +1,7 @@
 // mapper.cpp — vr::Mapper on the device: creation, frame slots, the stitch of one frame and of a batch,
 // timing read-back and the traffic model.  Host orchestration only; the kernels are in the *.hip files.
 #include "mapper.hpp"
+#include "overlay_list.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,59 @@ void ensure_result(octvr_mapper& m) {
     m.result_view.upload(&v, 1);
 }
 
+// The copy chain over cameras [first, last) resolved per output pixel (composite_lut_kernel): the last one
+// whose mask is set wins.  The cameras before `first` take part with an empty ROI, so an entry's camera is
+// the frame index.  Per-camera templates -> device, the LUT back, the per-camera maps dropped.
+template <class Camera>
+std::vector<CompositeEntry> winner_lut(const octvr_mapper& m, const Camera& camera, int first, int last) {
+    std::vector<DevBuf<float>> m1(last), m2(last);
+    std::vector<DevBuf<uint8_t>> mk(last);
+    std::vector<CamTemplate> ct(last, CamTemplate{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0});
+    for (int i = first; i < last; i++) {
+        const RigInput& in = camera(i);
+        m1[i].upload(in.map1.data(), in.map1.size());
+        m2[i].upload(in.map2.data(), in.map2.size());
+        mk[i].upload(in.mask.data(), in.mask.size());
+        ct[i] = CamTemplate{m1[i].p, m2[i].p, mk[i].p, in.roi[0], in.roi[1], in.roi[2], in.roi[3], m.in_w[i], m.in_h[i]};
+    }
+    DevBuf<CamTemplate> ctd;
+    ctd.upload(ct.data(), ct.size());
+    DevBuf<CompositeEntry> lut;
+    lut.alloc((size_t)m.W * m.H);
+    HIP_CHECK(launch_composite_lut(ctd.p, last, m.W, m.H, lut.p, nullptr, m.tex));
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<CompositeEntry> lut8((size_t)m.W * m.H);
+    HIP_CHECK(hipMemcpy(lut8.data(), lut.p, lut8.size() * sizeof(CompositeEntry), hipMemcpyDeviceToHost));
+    return lut8;
+}
+
+// The overlays of a multi-band / feather mapper (cameras N .. N + K - 1): their winner LUT, the pixels some
+// overlay's mask covers marked (a covered pixel whose entry is invalid is still written, black), cut down to
+// overlay_apply_kernel's work list; the taps it reads join the mapper's footprint.
+template <class Camera>
+void setup_overlays(octvr_mapper& m, const Camera& camera) {
+    std::vector<CompositeEntry> lut = winner_lut(m, camera, m.n, m.nc);
+    for (int i = m.n; i < m.nc; i++) {
+        const RigInput& in = camera(i);
+        for (int ry = 0; ry < in.roi[3]; ry++)
+            for (int rx = 0; rx < in.roi[2]; rx++) {
+                const int x = in.roi[0] + rx, y = in.roi[1] + ry;
+                if (x < 0 || y < 0 || x >= m.W || y >= m.H || !in.mask[(size_t)ry * in.roi[2] + rx]) continue;
+                lut[(size_t)y * m.W + x].code |= kCodeCovered;
+            }
+    }
+    const OverlayListBuild<CompositeEntry> b = build_overlay_list(lut, m.W, m.H, kCodeCovered, kOvBlockGroups);
+    SourceFootprint taps;
+    taps.init(m.in_w, m.in_h);
+    for (const CompositeEntry& e : b.entries) taps.mark_taps(e);
+    m.foot.merge(taps);
+    m.ov.covered = b.covered;
+    m.ov.source_bytes = taps.bytes();
+    m.ov.groups.upload(b.groups.data(), b.groups.size());
+    m.ov.entries.upload(b.entries.data(), b.entries.size());
+    m.ov.view = OverlayList{m.ov.groups.p, m.ov.entries.p, (int)b.groups.size()};
+}
+
 void check_out_pitch(const octvr_mapper* m, size_t out_pitch) {
     REQUIRE(out_pitch >= (size_t)m->SW, "output pitch smaller than width");
     // the stitch kernel addresses the output through a buffer resource with 32-bit offsets
@@ -39,7 +93,7 @@ void check_out_pitch(const octvr_mapper* m, size_t out_pitch) {
 FrameSet frame_set(const octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch) {
     FrameSet fs;
     memset(&fs, 0, sizeof fs);
-    for (int i = 0; i < m->n; i++) fs.f[i] = checked_source_frame(in_dev[i], in_pitch[i], m->in_w[i], m->in_h[i], m->vig[i].p);
+    for (int i = 0; i < m->nc; i++) fs.f[i] = checked_source_frame(in_dev[i], in_pitch[i], m->in_w[i], m->in_h[i], m->vig[i].p);
     return fs;
 }
 
@@ -174,8 +228,10 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
     TimedPair ev(m);
     hipEvent_t e0 = ev.e0, e1 = ev.e1;
     const bool timed = e0 != nullptr;
+    // overlays after a blend are copied onto the RGB(A) result too (mapper.cpp:279-287)
+    const bool overlays = m->ov.view.n_groups > 0;
     if (timed && (m->scaled || m->mb || preview)) HIP_CHECK(hipEventRecord(e0, s));  // else the composite records its own
-    if (m->scaled || preview) {
+    if (m->scaled || preview || overlays) {
         // stitch at template size into the RGB(A) result, then resize + RGB -> YUV420P (mapper.cpp:290-306)
         // (one frame slot only: the result frame is shared); without scaling the resize is the identity
         if (m->mb)
@@ -183,6 +239,7 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
         else
             HIP_CHECK(launch_mb_remap(fs, m->tiles.view, sl.gains, m->use_gain,
                                       RgbaOut{m->result.p, (uint32_t)m->result.n, m->result_view.p}, s, m->pix));
+        if (overlays) HIP_CHECK(launch_overlay_apply(fs, m->ov.view, m->result.p, (int64_t)m->W * 4, s, m->pix));
         HIP_CHECK(launch_resize_rgba_yuv420(m->result.p, m->W, m->H, (int64_t)m->W * 4, out_dev, m->SW, m->SH,
                                             (int64_t)out_pitch, s, (m->pix & kPixOutNv12) != 0));
         if (preview)  // cuda::resize(result, preview_output, ...) (mapper.cpp:308-312)
@@ -212,16 +269,16 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
     for (int f = 0; f < nb; f++) REQUIRE(out_dev[f], "NULL output");
     if (nb == 1 || m->scaled || m->mb) {
         for (int f = 0; f < nb; f++)
-            mapper_stitch(m, in_dev + (size_t)f * m->n, in_pitch + (size_t)f * m->n, out_dev[f], out_pitch,
+            mapper_stitch(m, in_dev + (size_t)f * m->nc, in_pitch + (size_t)f * m->nc, out_dev[f], out_pitch,
                           gains ? gains + (size_t)f * m->n : nullptr, gains ? m->n : 0, nullptr, s);
         return;
     }
     REQUIRE((int)m->slots.size() >= nb, "a batch of n frames needs n frames in flight (octvr_mapper_set_frames_in_flight)");
-    REQUIRE(nb <= 2 || m->n <= 16, "a batch of 4 frames holds 16 cameras per frame");
+    REQUIRE(nb <= 2 || m->nc <= 16, "a batch of 4 frames holds 16 cameras per frame (inputs and overlays)");
     check_out_pitch(m, out_pitch);
     DeviceGuard dg(m->device);
     FrameSet fs[kMaxBatch];  // every frame checked before any of them puts work on the stream
-    for (int f = 0; f < nb; f++) fs[f] = frame_set(m, in_dev + (size_t)f * m->n, in_pitch + (size_t)f * m->n);
+    for (int f = 0; f < nb; f++) fs[f] = frame_set(m, in_dev + (size_t)f * m->nc, in_pitch + (size_t)f * m->nc);
     const double* g[kMaxBatch];
     octvr_mapper::FrameSlot* sl[kMaxBatch];
     const bool feed = m->use_gain && !gains && m->n_chunks > 0;  // every frame's gains estimated: one feed launch
@@ -289,16 +346,18 @@ std::unique_ptr<octvr_mapper> mapper_create(const octvr_rig* rig, int device, in
                                             int flags) {
     REQUIRE(rig && in_w && in_h, "NULL argument");
     REQUIRE((flags & ~OCTVR_REMAP_TEXTURE) == 0, "unknown mapper flags");
-    if (!rig->overlays.empty())  // checked first: the real reason, whatever n_inputs says
-        throw OctvrError(OCTVR_E_UNSUPPORTED, "overlay inputs are not implemented in this ABI version");
-    REQUIRE(n_inputs == (int)rig->inputs.size(), "in_sizes must cover every input");
-    REQUIRE((int)rig->inputs.size() <= kMaxCams, "too many inputs");
+    // the frames of a stitch: every input, then every overlay (mapper.cpp:208, inputs.size() == masks.size())
+    const int n_in = (int)rig->inputs.size(), n_ov = (int)rig->overlays.size();
+    REQUIRE(n_in + n_ov <= kMaxCams, "too many inputs and overlays");
+    REQUIRE(n_inputs == n_in + n_ov, n_ov ? "in_sizes must cover every input and every overlay (N + K)"
+                                          : "in_sizes must cover every input");
     REQUIRE(scale_w >= 0 && scale_h >= 0 && (scale_w == 0) == (scale_h == 0), "bad scaled output size");
     REQUIRE(rig->out_w % 2 == 0 && rig->out_h % 2 == 0, "YUV420 output needs even width/height");
     auto m = std::make_unique<octvr_mapper>();
     m->device = device;
     m->tex = (flags & OCTVR_REMAP_TEXTURE) ? 1 : 0;
-    m->n = (int)rig->inputs.size();
+    m->n = n_in;
+    m->nc = n_in + n_ov;
     m->W = rig->out_w;
     m->H = rig->out_h;
     // scaled_output_size = scale_output.area() == 0 ? mt.out_size : scale_output (mapper.cpp:69)
@@ -309,20 +368,22 @@ std::unique_ptr<octvr_mapper> mapper_create(const octvr_rig* rig, int device, in
     REQUIRE(!m->scaled || (uint64_t)m->W * m->H * 4 < 0x7FFFFF80ull, "stitch frame larger than 2 GiB as RGBA");
     m->in_w.assign(in_w, in_w + n_inputs);
     m->in_h.assign(in_h, in_h + n_inputs);
-    for (int i = 0; i < m->n; i++)
+    for (int i = 0; i < m->nc; i++)
         REQUIRE(m->in_w[i] > 0 && m->in_h[i] > 0 && m->in_w[i] % 2 == 0 && m->in_h[i] % 2 == 0 &&
                     m->in_w[i] <= 65535 && m->in_h[i] <= 65535,
-                "input sizes must be even and < 65536");
-    // mapper.cpp:78-82: a single input disables gain (and blend)
+                "input and overlay sizes must be even and < 65536");
+    // mapper.cpp:78-82: a single input disables gain (and blend), whatever overlays it has
     m->use_gain = (enable_gain && m->n > 1) ? 1 : 0;
     m->blend = m->n > 1 ? blend : 0;
     REQUIRE(!m->use_gain || m->n <= 16, "gain estimation supports at most 16 inputs");
     DeviceGuard dg(device);
+    // camera i of the stitch: input i, or overlay i - N
+    auto camera = [&](int i) -> const RigInput& { return i < n_in ? rig->inputs[i] : rig->overlays[i - n_in]; };
     // vignette: cv::cuda::resize(vignette, vignette_maps[i], in_size) (mapper.cpp:108-112), applied to
-    // every source pixel before the remap (mapper.cpp:230-231)
-    m->vig.resize(m->n);
-    for (int i = 0; i < m->n; i++) {
-        const RigInput& in = rig->inputs[i];
+    // every source pixel before the remap (mapper.cpp:230-231), overlays included
+    m->vig.resize(m->nc);
+    for (int i = 0; i < m->nc; i++) {
+        const RigInput& in = camera(i);
         if (in.vignette.empty()) continue;
         const std::vector<float> v = resize_linear_f32(in.vignette.data(), in.vig_w, in.vig_h, m->in_w[i], m->in_h[i]);
         m->vig[i].upload(v.data(), v.size());
@@ -336,37 +397,17 @@ std::unique_ptr<octvr_mapper> mapper_create(const octvr_rig* rig, int device, in
         // FeatherGPUBlender(masks, rois, border = -blend) (mapper.cpp:177-182)
         m->mb.reset(multiband_create(*rig, device, 0, m->in_w, m->in_h, -m->blend, &m->foot, m->tex));
     } else {
-        // per-camera templates -> device, composite LUT, then drop the per-camera maps
-        std::vector<DevBuf<float>> m1(m->n), m2(m->n);
-        std::vector<DevBuf<uint8_t>> mk(m->n);
-        std::vector<CamTemplate> ct(m->n);
-        for (int i = 0; i < m->n; i++) {
-            const RigInput& in = rig->inputs[i];
-            m1[i].upload(in.map1.data(), in.map1.size());
-            m2[i].upload(in.map2.data(), in.map2.size());
-            mk[i].upload(in.mask.data(), in.mask.size());
-            ct[i] = CamTemplate{m1[i].p, m2[i].p, mk[i].p, in.roi[0], in.roi[1], in.roi[2], in.roi[3],
-                                m->in_w[i], m->in_h[i]};
-        }
-        DevBuf<CamTemplate> ctd;
-        ctd.upload(ct.data(), ct.size());
-        DevBuf<CompositeEntry> lut;
-        lut.alloc((size_t)m->W * m->H);
-        HIP_CHECK(launch_composite_lut(ctd.p, m->n, m->W, m->H, lut.p, nullptr, m->tex));
-        HIP_CHECK(hipDeviceSynchronize());
-        std::vector<CompositeEntry> lut8((size_t)m->W * m->H);
-        HIP_CHECK(hipMemcpy(lut8.data(), lut.p, lut8.size() * sizeof(CompositeEntry), hipMemcpyDeviceToHost));
-        lut.reset();
-        for (int i = 0; i < m->n; i++) {
-            m1[i].reset();
-            m2[i].reset();
-            mk[i].reset();
-        }
+        // per-camera templates -> device, composite LUT, then drop the per-camera maps.  The overlays are the
+        // last cameras of the copy chain (mapper.cpp:279-287 after :268-277), so they win their pixels in the
+        // same LUT and the stitch does no extra work for them; their gain stays the slot's constant 1
+        // (make_slot), and sat_u8(px * 1.0f) = px.
+        const std::vector<CompositeEntry> lut8 = winner_lut(*m, camera, 0, m->nc);
         const TiledLutBuild tb = build_frame_tiles(lut8, m->W, m->H, m->in_w, m->in_h, &m->n_tiles);
         footprint_add_tiles(m->foot, tb);
         m->tiles.upload(tb);
     }
-    if (m->scaled) ensure_result(*m);
+    if (m->mb && n_ov) setup_overlays(*m, camera);
+    if (m->scaled || m->ov.view.n_groups) ensure_result(*m);
     m->last_gains.assign(m->n, 1.0);
     if (m->use_gain) setup_gain(*m, *rig);
     m->slots.push_back(make_slot(*m));
@@ -383,6 +424,8 @@ void mapper_set_frames_in_flight(octvr_mapper* m, int k) {
     REQUIRE(m && k >= 1 && k <= OCTVR_MAX_FRAMES_IN_FLIGHT, "frames in flight must be 1..OCTVR_MAX_FRAMES_IN_FLIGHT");
     if (k > 1 && m->scaled)
         throw OctvrError(OCTVR_E_UNSUPPORTED, "frames in flight > 1 need the output at template size (no scaled output)");
+    if (k > 1 && m->ov.view.n_groups)  // the overlays are copied onto the one result frame
+        throw OctvrError(OCTVR_E_UNSUPPORTED, "frames in flight > 1 with overlays need blend 0 (no multi-band or feather)");
     DeviceGuard dg(m->device);
     mapper_sync(*m);
     if (m->cur_slot != 0) {  // keep the last frame's gains for gains() / chaining
@@ -446,6 +489,12 @@ double mapper_traffic(const octvr_mapper* m) {
     // pixel, the unique source bytes its staged boxes cover (YUV420P, 1.5 B per luma pixel: the
     // circular crops leave the rest of each frame unread), tile headers / slots.  Multi-band: the
     // sum over the sequence's launches (multiband_traffic_parts).
+    // Overlays after a blend: the blend's result as RGBA written (by the blend, counted there as its YUV
+    // output) and read back by the identity resize, the work list (4 B per group + 8 B per entry), the
+    // unique source bytes under the overlays' taps and 4 B per covered pixel written.
+    if (m->mb && m->ov.view.n_groups)
+        return multiband_traffic(*m->mb) + 4.0 * m->W * m->H + 1.5 * m->SW * m->SH +
+               (double)m->ov.view.n_groups * (4.0 + 8.0 * kOvGroupPx) + m->ov.source_bytes + 4.0 * (double)m->ov.covered;
     if (m->mb) return multiband_traffic(*m->mb);
     return tiled_lut_bytes(m->tiles.view) + 1.5 * m->W * m->H + m->tiles.source_bytes;
 }

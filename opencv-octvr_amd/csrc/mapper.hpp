@@ -15,7 +15,8 @@ struct octvr_mapper {
     template <class T>
     using DevBuf = octvr::DevBuf<T>;
     int device = 0;
-    int n = 0;
+    int n = 0;   // inputs N: what the gain estimation and the blenders see
+    int nc = 0;  // cameras N + K: the frames of a stitch call, the K overlays at the tail (camera N + k)
     int W = 0, H = 0;
     int use_gain = 0;
     std::vector<int> in_w, in_h;
@@ -41,6 +42,10 @@ struct octvr_mapper {
     bool scaled = false;
     DevBuf<uint8_t> result;
     DevBuf<octvr::MbCamLevel> result_view;  // the result frame as a one-entry RGBA sink of the composite
+    // Overlays of a multi-band / feather mapper: the work list of overlay_apply_kernel (overlay.hip), which
+    // copies the overlays onto the result frame after the blend.  A blend-0 mapper has none: its overlays
+    // are cameras of the composite LUT.
+    octvr::OverlayListDev ov;
     // Per-frame device state that consecutive stitches would otherwise share: the gains, the feed's
     // pair totals and tickets, the composite's work queue.  A mapper is created with one slot;
     // octvr_mapper_set_frames_in_flight adds slots so that stitches issued on different streams overlap

@@ -487,14 +487,15 @@ int octvr_mapper_kernel_intervals(octvr_mapper* m, double* start_ms, double* end
 int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
     return guarded([&] {
         REQUIRE(m && buf && len > 0, "bad arguments");
-        char tmp[512];
+        char tmp[768];
         snprintf(tmp, sizeof tmp,
                  "{\"inputs\": %d, \"out\": [%d, %d], \"blend\": %d, \"tiles\": %d, \"wide_tiles\": %d, "
                  "\"staged_bytes\": %.0f, \"source_bytes\": %.0f, \"gain\": %d, \"gain_samples\": %d, \"gain_pairs_px\": %zu, "
-                 "\"gain_chunks\": %d, \"scaled_out\": [%d, %d], \"footprint_bytes\": %.0f",
+                 "\"gain_chunks\": %d, \"scaled_out\": [%d, %d], \"footprint_bytes\": %.0f, \"overlays\": %d, "
+                 "\"overlay_groups\": %d, \"overlay_px\": %zu",
                  m->n, m->W, m->H, m->blend, m->n_tiles, m->tiles.view.n_wide,
                  m->mb ? 0.0 : m->tiles.staged_bytes, m->mb ? 0.0 : m->tiles.source_bytes, m->use_gain, m->n_samples, m->n_entries, m->n_chunks, m->SW, m->SH,
-                 m->foot.bytes());
+                 m->foot.bytes(), m->nc - m->n, m->ov.view.n_groups, m->ov.covered);
         std::string js = tmp;
         if (m->mb) js += ", " + multiband_info(*m->mb);
         else if (!m->tiles.stats.empty()) js += ", " + m->tiles.stats;

@@ -494,7 +494,13 @@ def yuv420p_from_nv12(frame, w, h):
 
 
 class Mapper:
-    """vr::Mapper on one device: stitch(inputs YUV420P, output YUV420P) with optional gain."""
+    """vr::Mapper on one device: stitch(inputs YUV420P, output YUV420P) with optional gain.
+
+    A template with K overlays (mt.num_overlays) takes N + K in_sizes and N + K frames per stitch: the tail
+    frames are the overlays' live frames, in overlay order, each of its own (even) size.  They are warped
+    like the inputs (vignette included), never gained or blended, and copied onto the blended result where
+    their mask is set, a later overlay over an earlier one, before the scaled output and the preview are
+    taken.  gains() and the `gains` argument keep one entry per input (N)."""
 
     def __init__(self, mt, in_sizes, blend=0, enable_gain=True, device=0, scale_output=(0, 0), remap="remap"):
         """remap: "remap" (cv::remap's fixed point, the default) or "texture" (the reference's CUDA
@@ -513,7 +519,8 @@ class Mapper:
             _check(_lib.octvr_mapper_create(mt._h, device, n, w, h, blend, int(enable_gain), scale_output[0],
                                             scale_output[1], C.byref(hd)))
         self._h = hd
-        self.n = n
+        self.n = n  # frames per stitch: inputs, then overlays
+        self.n_gains = n - mt.num_overlays
         self.device = device
         # output frame size: scale_output, or the template's out_size (mapper.cpp:69)
         self.out_size = tuple(scale_output) if scale_output[0] else mt.out_size
@@ -533,6 +540,8 @@ class Mapper:
             n = len(inputs)
             ptrs = (_VP * n)(*[t.data_ptr() for t in inputs])
             pitches = (C.c_size_t * n)(*[t.stride(0) for t in inputs])
+        if n != self.n:
+            raise ValueError("stitch takes %d frames (every input, then every overlay), got %d" % (self.n, n))
         g = None
         ng = 0
         if gains is not None:
@@ -567,14 +576,14 @@ class Mapper:
                                               _stream_ptr(stream)))
 
     def gains(self):
-        g = (C.c_double * self.n)()
-        _check(_lib.octvr_mapper_gains(self._h, g, self.n))
+        g = (C.c_double * self.n_gains)()
+        _check(_lib.octvr_mapper_gains(self._h, g, self.n_gains))
         return list(g)
 
     def set_frames_in_flight(self, k):
         """k slots of per-frame device state: stitches issued on different streams overlap
-        (octvr_mapper_set_frames_in_flight).  No scaled output; multi-band / feather mappers get
-        per-slot pyramids."""
+        (octvr_mapper_set_frames_in_flight).  No scaled output, and no overlays on a multi-band / feather
+        mapper (one result frame); multi-band / feather mappers get per-slot pyramids."""
         _check(_lib.octvr_mapper_set_frames_in_flight(self._h, int(k)))
 
     def set_pixel_formats(self, in_format="yuv420p", out_format="yuv420p"):
@@ -700,8 +709,11 @@ class AsyncMultiMapper:
     a 3-deep pinned-buffer pipeline (copy-in, H2D, stitch, D2H, copy-out overlap across frames).  Either side
     may be NV12 instead (set_pixel_formats): its plane sets are then (Y, UV) two-tuples.
 
-    templates: list of MapperTemplate (all with the same inputs); output_regions: list of (x, y, w, h)
-    fractions of out_size; gain_modes[i]: -1 no gain, i estimate, j < i reuse mapper j's gains.
+    templates: list of MapperTemplate over the same len(in_sizes) frames: each template's inputs plus its
+    overlays number len(in_sizes) (the split may differ per template; the overlays' frames are the tail, as
+    for Mapper); output_regions: list of (x, y, w, h)
+    fractions of out_size; gain_modes[i]: -1 no gain, i estimate, j < i reuse mapper j's gains (template j
+    then has as many inputs as template i).
     preview_size (w, h): AsyncMultiMapper::New's preview — each mapper also writes its region of one RGB
     preview image every frame (async.cpp:73-110); read the latest with preview(), or receive every one
     through set_preview_sink()."""
