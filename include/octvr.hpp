@@ -561,6 +561,14 @@ public:
     virtual void push(std::vector<std::tuple<cv::Mat, cv::Mat, cv::Mat>>& inputs,
                       std::tuple<cv::Mat, cv::Mat, cv::Mat>& output) = 0;
     virtual void pop() = 0;
+    // Not in the reference: push for frames that live on the device (octvr_hip.h octvr_async_push_device).  in:
+    // one device frame per input, then per overlay ("Y over [U|V]" or NV12 as set_pixel_formats says, W x 3H/2
+    // bytes at in_pitch[i] >= W); out: the merged device frame (out_size.width x 3 out_size.height / 2 bytes at
+    // out_pitch); ready: a hipEvent_t the stitch waits for before it reads the inputs, or nullptr.  pop()
+    // returns once the merged frame is complete on the device; the frames stay the caller's and must stay
+    // allocated and untouched until then.  push and push_device may be mixed.
+    virtual void push_device(const std::vector<const uint8_t*>& in, const std::vector<size_t>& in_pitch, uint8_t* out,
+                             size_t out_pitch, void* ready = nullptr) = 0;
     // Not in the reference: the pixel layouts of the host planes, OCTVR_PIX_YUV420P (the default) or
     // OCTVR_PIX_NV12, for the inputs (all alike) and the output independently (octvr_hip.h
     // octvr_async_set_pixel_formats; no frame may be pending).  With NV12 the second cv::Mat of an input or
@@ -643,6 +651,13 @@ public:
         hold.push_back(std::get<2>(output));
         check(octvr_async_push(a_, in.data(), ip.data(), out, op));
         held_.push_back(std::move(hold));
+    }
+    void push_device(const std::vector<const uint8_t*>& in, const std::vector<size_t>& in_pitch, uint8_t* out,
+                     size_t out_pitch, void* ready = nullptr) override {
+        if ((int)in.size() != n_ || (int)in_pitch.size() != n_)
+            throw cv::Exception(OCTVR_E_INVALID, "input count does not match");
+        check(octvr_async_push_device(a_, in.data(), in_pitch.data(), out, out_pitch, ready));
+        held_.push_back(Held());  // nothing to keep alive: device frames are the caller's
     }
     void pop() override {
         const int rc = octvr_async_pop(a_);

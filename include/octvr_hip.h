@@ -303,12 +303,15 @@ int octvr_async_pop_preview(octvr_async* async, uint8_t* rgb, size_t pitch, octv
 /* Called on the pipeline's copy-out thread for every frame's preview, after that frame's outputs are written
  * and before its pop() returns (the reference's Qt shared-memory write, async.cpp:149-171): rgb = the
  * downloaded preview (host, valid during the call only), pitch = preview_w * 3.  A Qt caller writes it into
- * zone *meta of its two QSharedMemory zones.  NULL removes the sink. */
+ * zone *meta of its two QSharedMemory zones.  NULL removes the sink.  The sink runs with no
+ * lock of the pipeline held: it may call octvr_async_pop_preview or octvr_async_set_preview_sink.  Called from
+ * any other thread, octvr_async_set_preview_sink returns after a running sink call has returned. */
 typedef void (*octvr_preview_sink)(void* user, const uint8_t* rgb, size_t pitch, const octvr_preview_header* hdr);
 int octvr_async_set_preview_sink(octvr_async* async, octvr_preview_sink sink, void* user);
 /* Build-time facts of the pipeline as a JSON object: packed_bytes (the footprint bytes uploaded per frame,
  * run gaps included), runs, frame bytes, preview size, the mappers' creation flags, and "pixel_formats":
- * [in, out], the current OCTVR_PIX_* pair. */
+ * [in, out], the current OCTVR_PIX_* pair; "device_frames", the frames octvr_async_push_device has queued so
+ * far, and "merge_launches", the merge kernel's launches for them (0 or 1 per device frame). */
 int octvr_async_info(const octvr_async* async, char* buf, size_t len);
 /* Pixel layouts of the pipeline's host planes (no reference counterpart: the reference's planes are planar;
  * decoders, capture cards and encoders speak NV12): OCTVR_PIX_YUV420P (the default) or OCTVR_PIX_NV12, for the
@@ -338,8 +341,36 @@ int octvr_async_pixel_formats(const octvr_async* async, int* in_format, int* out
  * matching pop. */
 int octvr_async_push(octvr_async* async, const uint8_t* const* in_planes, const size_t* in_pitches,
                      uint8_t* const* out_planes, const size_t* out_pitches);
-/* pop() (async.cpp:191-193): blocks until the oldest pushed frame has been written to its output planes;
- * returns that frame's status (OCTVR_E_INVALID if nothing is pending). */
+/* push for frames that already live on the device (no reference counterpart: a decoder, a capture DMA, a
+ * tensor or another kernel wrote them, and an encoder or a model reads the result there).
+ *   in_dev[i] / in_pitch[i], i < n_inputs: one device frame per input, then per overlay, in the layout
+ *     octvr_mapper_stitch_yuv420p takes: W x 3H/2 bytes, pitch >= W, any alignment; "Y over [U|V]" or NV12 as
+ *     the pipeline's input format says (octvr_async_set_pixel_formats).
+ *   out_dev / out_pitch: the merged device frame, out_w x 3 out_h / 2 bytes, pitch >= out_w, in the
+ *     pipeline's output format.  Region k's bytes land where push puts them in the host planes: Y at its
+ *     rectangle r; planar chroma at its chroma rectangle c of the U half (columns [0, out_w / 2) of the rows
+ *     from out_h) and of the V half (columns from out_w / 2); NV12 chroma at bytes [2 c.x, 2 c.x + 2 c.w) of
+ *     rows out_h + [c.y, c.y + c.h).  Bytes outside every region, and between out_w and the pitch, are never
+ *     written.
+ *   ready_event: a hipEvent_t the pipeline's compute stream waits for before any kernel reads the inputs;
+ *     NULL: the inputs are complete already.
+ * No host staging, no upload and no download for such a frame: the mappers read the caller's frames in
+ * place and stitch into the pipeline's region frames, gains chained and the preview written as for push, then
+ * one kernel places every region into the merged frame (a single region covering the whole output is
+ * stitched straight into out_dev).  The preview, a small host image, is still downloaded and published.
+ * Returns once the frame is queued.  octvr_async_pop returns its status once the merged frame is complete on
+ * the device, the compute stream synchronised: the caller may then read it from any stream.  The frames must
+ * stay allocated and untouched until that pop.  push and push_device may be mixed; pop order is push order
+ * and octvr_async_pending counts both.
+ * OCTVR_E_INVALID, with nothing queued or launched: a NULL pointer; a pitch below the width; an output frame
+ * of 2 GiB or more or an input frame beyond the mappers' limits; in_dev[i] or out_dev that
+ * hipPointerGetAttributes does not report as device memory of the pipeline's device (host memory, pinned
+ * memory included); more than 32 regions (one merge launch's table). */
+int octvr_async_push_device(octvr_async* async, const uint8_t* const* in_dev, const size_t* in_pitch,
+                            uint8_t* out_dev, size_t out_pitch, void* ready_event);
+/* pop() (async.cpp:191-193): blocks until the oldest pushed frame has been written to its output planes
+ * (octvr_async_push_device: to its merged device frame); returns that frame's status (OCTVR_E_INVALID if
+ * nothing is pending). */
 int octvr_async_pop(octvr_async* async);
 /* Register an output plane set (Y, U, V of out_w x out_h, out_w/2 x out_h/2, ...) that the caller reuses
  * (a ring of output frames, as the reference reuses its output Mats, async.cpp:113-138): the planes are

@@ -25,9 +25,13 @@
 //     (octvr_async_pop_preview / octvr_async_set_preview_sink) instead of Qt shared memory, which stays
 //     the caller's;
 //   * the host planes may be NV12 on either side (octvr_async_set_pixel_formats): the mappers read and write
-//     that layout themselves, and every stage here moves a Y plane and one U,V plane instead of three planes.
+//     that layout themselves, and every stage here moves a Y plane and one U,V plane instead of three planes;
+//   * frames that already live on the device skip the host stages (octvr_async_push_device): the mappers read
+//     the caller's device frames in place and one kernel (async_merge.hip) places the region frames into the
+//     caller's merged device frame; such frames travel the same queues, so pop order is push order.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -85,9 +89,7 @@ private:
     bool closed_ = false;
 };
 
-struct Rect {
-    int x, y, w, h;
-};
+using Rect = PlaneRect;
 
 // _rect_mul_size (async.cpp:20-30)
 Rect rect_mul_size(const double* r, int W, int H) {
@@ -162,6 +164,12 @@ struct Job {
     uint8_t* out_planes[3] = {nullptr, nullptr, nullptr};
     size_t out_pitches[3] = {0, 0, 0};
     bool direct = false;  // the output planes are registered: the D2H writes them, no copy-out
+    // octvr_async_push_device: in_planes / in_pitches hold one device frame per input, the merged frame is
+    // written on the device (no copy-in, upload, download or copy-out; the preview still comes down)
+    bool device = false;
+    uint8_t* out_dev = nullptr;
+    size_t out_pitch = 0;
+    hipEvent_t ready = nullptr;  // the compute stream waits for it before the first kernel (NULL: nothing)
     int slot = -1;
     int status = OCTVR_OK;
     std::string error;
@@ -270,6 +278,11 @@ struct octvr_async {
     octvr_preview_header pub_hdr{0, 0, 0, 0.0};
     octvr_preview_sink sink = nullptr;
     void* sink_user = nullptr;
+    // the sink runs outside pub_mu (it may call back into the preview API); a thread that replaces the sink
+    // waits for a running call to return, unless it is that call itself
+    bool sink_busy = false;
+    std::thread::id sink_thread;
+    std::condition_variable sink_idle;
     // fps over blocks of 10 frames, as the reference's copy-out thread keeps it (async.cpp:141-147): the
     // frame interval is measured from the previous frame's copy-out (the first from creation, fps_timer)
     std::chrono::steady_clock::time_point fps_t = std::chrono::steady_clock::now();
@@ -300,6 +313,11 @@ struct octvr_async {
     std::vector<std::thread> threads;
     RowPool copy_in_pool{kCopyHelpers}, copy_out_pool{kCopyHelpers};
     int pending = 0;  // pushed, not popped (caller thread only)
+    int64_t device_frames = 0;               // octvr_async_push_device calls that queued a frame (caller thread only)
+    std::atomic<int64_t> merge_launches{0};  // merge_regions_kernel launches (compute thread)
+    bool whole_frame_region() const {
+        return regions.size() == 1 && regions[0].x == 0 && regions[0].y == 0 && regions[0].w == out_w && regions[0].h == out_h;
+    }
 
     ~octvr_async() {
         q_in.close();
@@ -330,6 +348,7 @@ struct octvr_async {
         int s = -1;
         if (!free_slots.pop(s)) throw OctvrError(OCTVR_E_INVALID, "pipeline closed");
         j.slot = s;
+        if (j.device) return;  // the mappers read the caller's frames in place
         stage(j, [&] {
             uint8_t* const dst = slots[s].packed_host->p;
             copy_in_pool.run(runs.size(), [&](size_t lo, size_t hi) {
@@ -346,6 +365,7 @@ struct octvr_async {
     // run_upload_inputs_hostmem_to_gpumat (async.cpp:58-68): the packed runs, then one kernel puts them in
     // place in the device frames (bytes outside the footprint keep whatever they held: nothing reads them)
     void upload(Job& j) {
+        if (j.device) return;
         stage(j, [&] {
             DeviceGuard dg(device);
             Slot& sl = slots[j.slot];
@@ -366,9 +386,12 @@ struct octvr_async {
             std::vector<const uint8_t*> in(n_in);
             std::vector<size_t> pitch(n_in);
             for (int i = 0; i < n_in; i++) {
-                in[i] = sl.in_dev[i].p;
-                pitch[i] = (size_t)in_w[i];
+                in[i] = j.device ? j.in_planes[i] : sl.in_dev[i].p;
+                pitch[i] = j.device ? j.in_pitches[i] : (size_t)in_w[i];
             }
+            if (j.device && j.ready) HIP_CHECK(hipStreamWaitEvent(comp, j.ready, 0));
+            // a device frame's single region covering the whole output is stitched where it belongs
+            const bool in_place = j.device && whole_frame_region();
             for (size_t k = 0; k < mappers.size(); k++) {
                 const int gm = gain_modes[k];
                 const double* chained = nullptr;
@@ -382,8 +405,19 @@ struct octvr_async {
                     const size_t pp = (size_t)preview_w * 3;
                     pv = PreviewOut{sl.preview_dev.p + (size_t)r.y * pp + (size_t)r.x * 3, r.w, r.h, pp};
                 }
-                mapper_stitch(mappers[k], in.data(), pitch.data(), sl.out_dev[k].p, (size_t)regions[k].w, nullptr, 0,
-                              chained, comp, with_pv ? &pv : nullptr);
+                mapper_stitch(mappers[k], in.data(), pitch.data(), in_place ? j.out_dev : sl.out_dev[k].p,
+                              in_place ? j.out_pitch : (size_t)regions[k].w, nullptr, 0, chained, comp,
+                              with_pv ? &pv : nullptr);
+            }
+            if (j.device && !in_place) {  // every region frame into its place in the merged frame, one launch
+                std::vector<const uint8_t*> src;
+                for (auto& b : sl.out_dev) src.push_back(b.p);
+                MergeTable t;
+                REQUIRE(build_merge_table(regions.data(), regions_uv.data(), src.data(), (int)src.size(), out_w, out_h,
+                                          j.out_pitch, out_fmt == OCTVR_PIX_NV12, t),
+                        "regions do not fit a merge launch");
+                HIP_CHECK(launch_merge_regions(j.out_dev, t, comp));
+                merge_launches++;
             }
             HIP_CHECK(hipStreamSynchronize(comp));
         });
@@ -394,7 +428,7 @@ struct octvr_async {
         stage(j, [&] {
             DeviceGuard dg(device);
             Slot& sl = slots[j.slot];
-            for (size_t k = 0; k < mappers.size(); k++) {
+            for (size_t k = 0; k < mappers.size() && !j.device; k++) {
                 if (!j.direct) {
                     HIP_CHECK(hipMemcpyAsync(sl.out_host[k]->p, sl.out_dev[k].p, sl.out_host[k]->n, hipMemcpyDeviceToHost,
                                              down));
@@ -430,7 +464,7 @@ struct octvr_async {
     // run_copy_outputs_hostmem_to_mat (async.cpp:113-172)
     void copy_out(Job& j) {
         stage(j, [&] {
-            if (j.direct) return;  // the D2H wrote the caller's planes
+            if (j.direct || j.device) return;  // the D2H wrote the caller's planes / the frame stays on the device
             Slot& sl = slots[j.slot];
             for (size_t k = 0; k < mappers.size(); k++) {
                 const Rect& r = regions[k];
@@ -468,10 +502,26 @@ struct octvr_async {
         if (preview_w > 0 && j.status == OCTVR_OK) {
             const Slot& sl = slots[j.slot];
             const octvr_preview_header h{preview_w, preview_h, 0, frame_fps};
-            std::lock_guard<std::mutex> g(pub_mu);
-            memcpy(pub.data(), sl.preview_host->p, pub.size());
-            pub_hdr = h;
-            if (sink) sink(sink_user, sl.preview_host->p, (size_t)preview_w * 3, &h);
+            octvr_preview_sink call = nullptr;
+            void* user = nullptr;
+            {
+                std::lock_guard<std::mutex> g(pub_mu);
+                memcpy(pub.data(), sl.preview_host->p, pub.size());
+                pub_hdr = h;
+                call = sink;
+                user = sink_user;
+                sink_busy = call != nullptr;
+                sink_thread = std::this_thread::get_id();
+            }
+            // outside the lock: the sink may read the preview (octvr_async_pop_preview) or replace itself
+            if (call) {
+                call(user, sl.preview_host->p, (size_t)preview_w * 3, &h);
+                {
+                    std::lock_guard<std::mutex> g(pub_mu);
+                    sink_busy = false;
+                }
+                sink_idle.notify_all();
+            }
         }
     }
 
@@ -677,6 +727,49 @@ int octvr_async_push(octvr_async* a, const uint8_t* const* in_planes, const size
     return OCTVR_OK;
 }
 
+int octvr_async_push_device(octvr_async* a, const uint8_t* const* in_dev, const size_t* in_pitch, uint8_t* out_dev,
+                            size_t out_pitch, void* ready_event) {
+    return guarded([&] {
+        REQUIRE(a && in_dev && in_pitch && out_dev, "NULL argument");
+        REQUIRE(out_pitch >= (size_t)a->out_w, "output pitch smaller than width");
+        // the mappers' own limit (mapper.cpp check_out_pitch), and the merge's 32-bit offsets
+        REQUIRE((uint64_t)out_pitch * (uint64_t)(a->out_h + a->out_h / 2) < 0x7FFFFF80ull, "output frame larger than 2 GiB");
+        REQUIRE(a->whole_frame_region() || (int)a->regions.size() <= kMergeMaxRegions,
+                "more regions than one merge launch takes");
+        for (int i = 0; i < a->n_in; i++) {
+            REQUIRE(in_dev[i], "NULL input frame");
+            // the limits mapper_stitch sets (mapper.cpp checked_source_frame), refused here before anything is queued
+            REQUIRE(in_pitch[i] >= (size_t)a->in_w[i], "input pitch smaller than width");
+            REQUIRE(in_pitch[i] < ((size_t)1 << 24) &&
+                        (uint64_t)in_pitch[i] * (uint64_t)(a->in_h[i] + a->in_h[i] / 2) < 0x7FFFFFFFull,
+                    "input frame too large");
+        }
+        // a host pointer (pinned memory included: the kernels could read it, slowly) is refused before any launch
+        DeviceGuard dg(a->device);
+        auto on_device = [&](const void* p) {
+            hipPointerAttribute_t at;
+            memset(&at, 0, sizeof at);
+            if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+                (void)hipGetLastError();
+                return false;
+            }
+            return at.type == hipMemoryTypeDevice && at.device == a->device;
+        };
+        for (int i = 0; i < a->n_in; i++) REQUIRE(on_device(in_dev[i]), "input frame is not device memory of the pipeline's device");
+        REQUIRE(on_device(out_dev), "output frame is not device memory of the pipeline's device");
+        auto j = std::make_shared<Job>();
+        j->device = true;
+        j->in_planes.assign(in_dev, in_dev + a->n_in);
+        j->in_pitches.assign(in_pitch, in_pitch + a->n_in);
+        j->out_dev = out_dev;
+        j->out_pitch = out_pitch;
+        j->ready = static_cast<hipEvent_t>(ready_event);
+        a->q_in.push(std::move(j));
+        a->pending++;
+        a->device_frames++;
+    }, OCTVR_E_HIP);
+}
+
 int octvr_async_pop(octvr_async* a) {
     if (!a || a->pending <= 0) {
         set_last_error("no frame pending");
@@ -822,7 +915,8 @@ int octvr_async_set_preview_sink(octvr_async* a, octvr_preview_sink sink, void* 
         set_last_error("NULL argument");
         return OCTVR_E_INVALID;
     }
-    std::lock_guard<std::mutex> g(a->pub_mu);
+    std::unique_lock<std::mutex> g(a->pub_mu);
+    a->sink_idle.wait(g, [&] { return !a->sink_busy || a->sink_thread == std::this_thread::get_id(); });
     a->sink = sink;
     a->sink_user = user;
     return OCTVR_OK;
@@ -836,12 +930,14 @@ int octvr_async_info(const octvr_async* a, char* buf, size_t len) {
     size_t in_bytes = 0, out_bytes = 0;
     for (int i = 0; i < a->n_in; i++) in_bytes += (size_t)a->in_w[i] * (a->in_h[i] / 2 * 3);
     for (const Rect& r : a->regions) out_bytes += (size_t)r.w * (r.h / 2 * 3);
-    char tmp[640];
+    char tmp[768];
     snprintf(tmp, sizeof tmp,
              "{\"mappers\": %d, \"inputs\": %d, \"packed_bytes\": %zu, \"runs\": %zu, \"input_frame_bytes\": %zu, "
-             "\"output_bytes\": %zu, \"preview\": [%d, %d], \"flags\": %d, \"slots\": %d, \"pixel_formats\": [%d, %d]}",
+             "\"output_bytes\": %zu, \"preview\": [%d, %d], \"flags\": %d, \"slots\": %d, \"pixel_formats\": [%d, %d], "
+             "\"device_frames\": %lld, \"merge_launches\": %lld}",
              (int)a->mappers.size(), a->n_in, a->packed_bytes, a->runs.size(), in_bytes, out_bytes, a->preview_w,
-             a->preview_h, a->flags, kSlots, a->in_fmt, a->out_fmt);
+             a->preview_h, a->flags, kSlots, a->in_fmt, a->out_fmt, (long long)a->device_frames,
+             (long long)a->merge_launches.load());
     if (strlen(tmp) >= len) {
         set_last_error("buffer too small");
         return OCTVR_E_INVALID;

@@ -1,6 +1,8 @@
 // async_host.hpp — the AsyncMultiMapper pipeline's pure host arithmetic (no HIP, no device): the packing of
-// one footprint run from the caller's planes (async.cpp copy_in; debug_abi.cpp octvr_debug_pack_runs) and the
-// merge of the output planes' byte ranges before they are page-locked (octvr_async_register_output).
+// one footprint run from the caller's planes (async.cpp copy_in; debug_abi.cpp octvr_debug_pack_runs), the
+// merge of the output planes' byte ranges before they are page-locked (octvr_async_register_output), and the
+// region table and work-item arithmetic of the device-frame merge (octvr_async_push_device), which
+// merge_regions_kernel shares.
 #pragma once
 
 #include <algorithm>
@@ -59,6 +61,135 @@ inline std::vector<PinRange> merge_pin_ranges(std::vector<PinRange> in, uintptr_
         }
     }
     return out;
+}
+
+// ---- the merge of the regions into one device frame (octvr_async_push_device, async_merge.hip) ----------
+// The functions below run on the host and, compiled by hipcc, in merge_regions_kernel: one definition of the
+// arithmetic, checked on the CPU (tests/cpp/async_merge_check.cpp).
+#ifdef __HIPCC__
+#define OCTVR_MERGE_HD __host__ __device__
+#else
+#define OCTVR_MERGE_HD
+#endif
+
+struct PlaneRect {  // a rectangle of a plane, in the plane's own pixels
+    int x, y, w, h;
+};
+
+constexpr int kMergeMaxRegions = 32;  // regions of one merge launch (the table is a kernel argument)
+constexpr int kMergeChunk = 16;       // bytes of one work item's vector store
+
+// One region of the merged frame.  The source is the mapper's region frame, pitch = w: h rows of Y, then h / 2
+// chroma rows, each [U | V] halves of w / 2 bytes (planar output) or w bytes of U,V pairs (NV12).
+struct MergeRegion {
+    const uint8_t* src;
+    int w, h;
+    uint32_t y_off;  // byte offsets in the merged frame: the region's first Y byte,
+    uint32_t u_off;  // planar: its first U byte; NV12: the first byte of its first chroma row
+    uint32_t v_off;  // planar: its first V byte; NV12: unused (= u_off)
+    uint32_t first;  // index of the region's first work item
+};
+struct MergeTable {
+    uint32_t pitch;  // of the merged frame
+    int n, nv12;
+    uint32_t items;  // work items of all regions
+    MergeRegion r[kMergeMaxRegions];
+};
+
+// Work items of a row of n bytes: the bytes before the destination's first 16-byte boundary (item 0, at most
+// 15, possibly none), then 16-byte chunks, the last one possibly short.  An upper bound over every alignment.
+OCTVR_MERGE_HD inline uint32_t merge_row_items(int n) { return (uint32_t)((n + kMergeChunk - 1) / kMergeChunk + 1); }
+
+// Work items of a region, in order: h luma rows of merge_row_items(w); then per chroma row, NV12:
+// merge_row_items(w), planar: the U half's merge_row_items(w / 2), then the V half's.
+OCTVR_MERGE_HD inline uint64_t merge_region_items(int w, int h, int nv12) {
+    const uint64_t luma = (uint64_t)h * merge_row_items(w);
+    const uint64_t chroma = nv12 ? (uint64_t)(h / 2) * merge_row_items(w) : (uint64_t)(h / 2) * 2 * merge_row_items(w / 2);
+    return luma + chroma;
+}
+
+// The table for regions r (their rectangles in the Y plane) and c (in the U / V planes; c.w = r.w / 2 and
+// c.h = r.h / 2, octvr_async_create) of an out_w x out_h merged frame "Y over [U|V]" or NV12 at `pitch`.
+// false: more than kMergeMaxRegions regions, a rectangle outside the frame, or a frame of 2 GiB or more.
+inline bool build_merge_table(const PlaneRect* r, const PlaneRect* c, const uint8_t* const* src, int n, int out_w, int out_h,
+                              size_t pitch, int nv12, MergeTable& t) {
+    if (n <= 0 || n > kMergeMaxRegions || out_w <= 0 || out_h <= 0 || pitch < (size_t)out_w) return false;
+    if ((uint64_t)pitch * (uint64_t)(out_h + out_h / 2) >= 0x7FFFFF80ull) return false;
+    t.pitch = (uint32_t)pitch;
+    t.n = n;
+    t.nv12 = nv12 ? 1 : 0;
+    uint64_t items = 0;
+    for (int k = 0; k < n; k++) {
+        const PlaneRect &a = r[k], &b = c[k];
+        if (a.x < 0 || a.y < 0 || a.w <= 0 || a.h <= 0 || (a.w & 1) || (a.h & 1) || a.x + a.w > out_w || a.y + a.h > out_h)
+            return false;
+        if (b.x < 0 || b.y < 0 || b.w != a.w / 2 || b.h != a.h / 2 || b.x + b.w > out_w / 2 || b.y + b.h > out_h / 2)
+            return false;
+        MergeRegion& m = t.r[k];
+        m.src = src[k];
+        m.w = a.w;
+        m.h = a.h;
+        m.y_off = (uint32_t)((size_t)a.y * pitch + (size_t)a.x);
+        const size_t crow = (size_t)(out_h + b.y) * pitch;
+        m.u_off = (uint32_t)(crow + (nv12 ? 2 * (size_t)b.x : (size_t)b.x));
+        m.v_off = nv12 ? m.u_off : (uint32_t)(crow + (size_t)(out_w / 2) + (size_t)b.x);
+        m.first = (uint32_t)items;
+        items += merge_region_items(a.w, a.h, t.nv12);
+        if (items >= 0x7FFFFFFFull) return false;
+    }
+    for (int k = n; k < kMergeMaxRegions; k++) t.r[k] = MergeRegion{nullptr, 0, 0, 0, 0, 0, (uint32_t)items};
+    t.items = (uint32_t)items;
+    return true;
+}
+
+// What work item `id` (< t.items) copies: len bytes (0: nothing) from src to byte offset dst of the merged
+// frame, whose first byte is at address out_base (only its low four bits matter).  len = 16 only with dst
+// 16-byte aligned: the full chunks of a row start at the destination's first boundary.
+struct MergeSpan {
+    const uint8_t* src;
+    size_t dst;
+    int len;
+};
+OCTVR_MERGE_HD inline MergeSpan merge_item(const MergeTable& t, uint32_t id, uintptr_t out_base) {
+    int k = 0;
+    for (int i = 1; i < t.n; i++)
+        if (id >= t.r[i].first) k = i;
+    const MergeRegion m = t.r[k];
+    uint32_t local = id - m.first;
+    const uint32_t per_luma = merge_row_items(m.w), luma = (uint32_t)m.h * per_luma;
+    const uint8_t* s;
+    size_t d;
+    int n;
+    uint32_t chunk;
+    if (local < luma) {
+        const uint32_t row = local / per_luma;
+        chunk = local - row * per_luma;
+        s = m.src + (size_t)row * (size_t)m.w;
+        d = (size_t)m.y_off + (size_t)row * t.pitch;
+        n = m.w;
+    } else if (t.nv12) {
+        local -= luma;
+        const uint32_t row = local / per_luma;
+        chunk = local - row * per_luma;
+        s = m.src + ((size_t)m.h + row) * (size_t)m.w;
+        d = (size_t)m.u_off + (size_t)row * t.pitch;
+        n = m.w;
+    } else {
+        local -= luma;
+        const uint32_t per_half = merge_row_items(m.w / 2);
+        const uint32_t half_row = local / per_half;  // 2 * chroma row + (0: U, 1: V)
+        chunk = local - half_row * per_half;
+        const uint32_t row = half_row >> 1, v = half_row & 1u;
+        s = m.src + ((size_t)m.h + row) * (size_t)m.w + (v ? (size_t)(m.w / 2) : 0);
+        d = (size_t)(v ? m.v_off : m.u_off) + (size_t)row * t.pitch;
+        n = m.w / 2;
+    }
+    const int head = (int)((0 - (out_base + d)) & (uintptr_t)(kMergeChunk - 1));
+    const int h = head < n ? head : n;
+    if (chunk == 0) return MergeSpan{s, d, h};
+    const int b0 = h + kMergeChunk * (int)(chunk - 1);
+    if (b0 >= n) return MergeSpan{s, d, 0};
+    return MergeSpan{s + b0, d + (size_t)b0, n - b0 < kMergeChunk ? n - b0 : kMergeChunk};
 }
 
 }  // namespace octvr

@@ -284,6 +284,10 @@ hipError_t launch_unpack_runs(const uint8_t* packed, const FootRun* runs, int n_
 // launch_unpack_runs.
 hipError_t launch_unpack_runs_layout(const uint8_t* packed, const FootRun* runs, int n_runs, const FootFrames& frames,
                                      int nv12, hipStream_t s);
+// octvr_async_push_device's merge (async_merge.hip): every region frame of the table (async_host.hpp
+// build_merge_table) into its place in the merged device frame `out`, one launch.
+struct MergeTable;
+hipError_t launch_merge_regions(uint8_t* out, const MergeTable& t, hipStream_t s);
 
 struct TiledLut {
     const TileHdr* meta;          // per staged item kMetaWords 16-byte words: the TileHdr, then kTileSlots TileSlots

@@ -120,6 +120,8 @@ _lib.octvr_async_info.argtypes = [_VP, C.c_char_p, C.c_size_t]
 _lib.octvr_async_register_output.argtypes = [_VP, C.POINTER(_VP), C.POINTER(C.c_size_t)]
 _lib.octvr_async_unregister_output.argtypes = [_VP, C.POINTER(_VP)]
 _lib.octvr_async_push.argtypes = [_VP, C.POINTER(_VP), C.POINTER(C.c_size_t), C.POINTER(_VP), C.POINTER(C.c_size_t)]
+if hasattr(_lib, "octvr_async_push_device"):  # (absent from older libraries OCTVR_HIP_LIB may select for an A/B)
+    _lib.octvr_async_push_device.argtypes = [_VP, C.POINTER(_VP), C.POINTER(C.c_size_t), _VP, C.c_size_t, _VP]
 _lib.octvr_async_pop.argtypes = [_VP]
 _lib.octvr_async_pending.argtypes = [_VP, C.POINTER(C.c_int)]
 if hasattr(_lib, "octvr_async_set_pixel_formats"):  # (absent from older libraries OCTVR_HIP_LIB may select for an A/B)
@@ -707,7 +709,9 @@ class FastMapper:
 class AsyncMultiMapper:
     """vr::AsyncMultiMapper (modules/octvr/src/async.cpp): host YUV420P planes in, host planes out, through
     a 3-deep pinned-buffer pipeline (copy-in, H2D, stitch, D2H, copy-out overlap across frames).  Either side
-    may be NV12 instead (set_pixel_formats): its plane sets are then (Y, UV) two-tuples.
+    may be NV12 instead (set_pixel_formats): its plane sets are then (Y, UV) two-tuples.  Frames that already
+    live on the device go through push_device() instead of push(): cuda tensors in, one merged cuda tensor
+    out, no host copy; both kinds may be mixed on one pipeline.
 
     templates: list of MapperTemplate over the same len(in_sizes) frames: each template's inputs plus its
     overlays number len(in_sizes) (the split may differ per template; the overlays' frames are the tail, as
@@ -746,6 +750,7 @@ class AsyncMultiMapper:
         self._registered = []
         self._templates = list(templates)  # the mappers copy what they need; kept for symmetry with the reference
         self.n = n
+        self.in_sizes = [(int(s[0]), int(s[1])) for s in in_sizes]
         self.out_size = tuple(out_size)
         self._inflight = []
 
@@ -759,8 +764,43 @@ class AsyncMultiMapper:
         _check(_lib.octvr_async_push(self._h, ip, ipt, op, opt))
         self._inflight.append((planes, output))
 
+    @staticmethod
+    def _device_frame(t, w, h, what):
+        """t as a device frame of a w x h picture: a 2-D cuda uint8 tensor of 3h/2 rows and w columns with unit
+        column stride (a view of a larger tensor is fine: its row stride is the pitch)."""
+        if not (hasattr(t, "is_cuda") and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and
+                tuple(t.shape) == (h * 3 // 2, w) and t.stride(1) == 1):
+            raise ValueError("%s: expected a cuda uint8 tensor of shape (%d, %d) with unit column stride"
+                             % (what, h * 3 // 2, w))
+        return t
+
+    def push_device(self, inputs, output, ready=None):
+        """push() for frames that live on the device (octvr_async_push_device): inputs, one 2-D cuda uint8
+        tensor per input and then per overlay (3h/2 rows x w columns, "Y over [U|V]" or NV12 as the input
+        format says), are read in place; output, one such tensor of the merged frame (3H/2 x W), is written on
+        the device, bytes outside the regions and past the width untouched.  A tensor's row stride is its
+        pitch, so views of larger tensors work.  ready: a recorded torch.cuda.Event the stitch waits for before
+        it reads the inputs; None: the inputs are complete (synchronize the stream that wrote them first).
+        The tensors are kept alive until the matching pop(), which returns `output` once the merged frame is
+        complete on the device."""
+        if len(inputs) != self.n:
+            raise ValueError("push_device takes %d frames (every input, then every overlay), got %d"
+                             % (self.n, len(inputs)))
+        ins = [self._device_frame(t, w, h, "input %d" % i) for i, (t, (w, h)) in enumerate(zip(inputs, self.in_sizes))]
+        out = self._device_frame(output, self.out_size[0], self.out_size[1], "output")
+        ptrs = (_VP * self.n)(*[t.data_ptr() for t in ins])
+        pitches = (C.c_size_t * self.n)(*[t.stride(0) for t in ins])
+        ev = None
+        if ready is not None:
+            ev = C.c_void_p(ready.cuda_event)
+            if not ev.value:
+                raise ValueError("ready: the event has not been recorded")
+        _check(_lib.octvr_async_push_device(self._h, ptrs, pitches, C.c_void_p(out.data_ptr()), out.stride(0), ev))
+        self._inflight.append(((ins, ready), output))
+
     def pop(self):
-        """Blocks until the oldest pushed frame is written; returns its output planes."""
+        """Blocks until the oldest pushed frame is written; returns its output planes (push_device: its
+        output tensor)."""
         rc = _lib.octvr_async_pop(self._h)
         output = self._inflight.pop(0)[1] if self._inflight else None
         _check(rc)
