@@ -458,6 +458,12 @@ int octvr_debug_fastmapper_audit(const octvr_rig* rig, int n_inputs, const int* 
  * creation flags (OCTVR_REMAP_TEXTURE: texture-convention entries, interior ones staged, border tiles wide). */
 int octvr_debug_tiled_lut_info(const octvr_rig* rig, int n_inputs, const int* in_w, const int* in_h, int flags,
                                char* json, size_t len);
+/* The blend = 0 composite's 8-byte quad records (host only, no GPU): for each of n_quads quads of four 4-byte tiled
+ * entries of an item of LDS row stride `stride` (dwords), ok[q] = 1 and records[q] = its record where the quad
+ * qualifies (all black, or one slot and tap origins within {0, 1} x {0, 1} of a base), else ok[q] = 0 and
+ * records[q] = 0; unpacked[4 q ..] = the record decoded back by the kernel's arithmetic. */
+int octvr_debug_entry_pack(const uint32_t* entries, int n_quads, uint32_t stride, uint64_t* records, uint8_t* ok,
+                           uint32_t* unpacked);
 /* The gain feed's samples as octvr_mapper_create lays them out (host only, no GPU): per sample its entry
  * (samples[2k] = xy, samples[2k+1] = code, kernels.hpp CompositeEntry) and partner mask, in the order the
  * feed's waves take them (padding included).  count receives the number of samples; samples / partners

@@ -311,25 +311,36 @@ struct TileData {
 // scalar byte offset, so no per-lane 64-bit address is formed per item (TiledLutDev::upload checks
 // that the entries fit 32-bit offsets)
 // E24: the lane's four 24-bit entries of each half (tiled_entry24) as three dwords (d.e4[h].w unused)
-template <bool DWORD_STAGE, bool VIG, bool E24, int IN = kInPlanar>
-__device__ __forceinline__ void data_issue(const __amdgpu_buffer_rsrc_t& er, const TileMeta& m, int t_end, int lg,
-                                           const StageSlot& sl, uint32_t g, TileData& d, bool nv12 = false) {
+// EP: the instance of a LUT with quad-packed items (kItemPacked, wave-uniform per item).  Only the first 16 bytes
+// per lane are loaded ahead: a packed item's records of both halves (d.e4[0].x, .y and .z, .w), or half 0's
+// entries of an unpacked item, whose half 1 the compute phase loads itself (stitch_tiled_body) — 4 entry
+// registers in flight instead of 8, and the same instruction for either form, so no vector-memory operation
+// of the issue phase sits under the per-item branch
+//
+// entry_issue: the load of half h of item m's entries (16 bytes per lane at the item's scalar offset)
+template <bool E24, bool EP>
+__device__ __forceinline__ void entry_issue(const __amdgpu_buffer_rsrc_t& er, const TileMeta& m, int t_end, int lg, int h,
+                                            TileData& d) {
     const bool live = m.t < t_end;
     const int tid = threadIdx.x;
-#pragma unroll
-    for (int h = 0; h < kItemHalves; h++) {
-        const uint32_t so =
-            (uint32_t)uniform(((live ? m.t : 0) >> lg) * kItemHalves + h) * (uint32_t)(kTilePx * (E24 ? 3 : 4));
-        if constexpr (E24) {
-            typedef unsigned int u32x3e __attribute__((ext_vector_type(3)));
-            const u32x3e v = __builtin_amdgcn_raw_buffer_load_b96(er, (uint32_t)tid * 12u, so, 0);
-            d.e4[h] = uint4{v.x, v.y, v.z, 0u};
-        } else {
-            typedef unsigned int u32x4e __attribute__((ext_vector_type(4)));
-            const u32x4e v = __builtin_amdgcn_raw_buffer_load_b128(er, (uint32_t)tid * 16u, so, 0);
-            d.e4[h] = uint4{v.x, v.y, v.z, v.w};
-        }
+    const uint32_t so =
+        (uint32_t)uniform(((live ? m.t : 0) >> lg) * kItemHalves + h) * (uint32_t)(kTilePx * (E24 ? 3 : 4));
+    if constexpr (E24) {
+        typedef unsigned int u32x3e __attribute__((ext_vector_type(3)));
+        const u32x3e v = __builtin_amdgcn_raw_buffer_load_b96(er, (uint32_t)tid * 12u, so, 0);
+        d.e4[h] = uint4{v.x, v.y, v.z, 0u};
+    } else {
+        typedef unsigned int u32x4e __attribute__((ext_vector_type(4)));
+        const u32x4e v = __builtin_amdgcn_raw_buffer_load_b128(er, (uint32_t)tid * 16u, so, 0);
+        d.e4[h] = uint4{v.x, v.y, v.z, v.w};
     }
+}
+
+template <bool DWORD_STAGE, bool VIG, bool E24, int IN = kInPlanar, bool EP = false>
+__device__ __forceinline__ void data_issue(const __amdgpu_buffer_rsrc_t& er, const TileMeta& m, int t_end, int lg,
+                                           const StageSlot& sl, uint32_t g, TileData& d, bool nv12 = false) {
+#pragma unroll
+    for (int h = 0; h < (EP ? 1 : kItemHalves); h++) entry_issue<E24, EP>(er, m, t_end, lg, h, d);
     if (!sl.live) {  // wave-uniform: no loads for a chunk the item lacks
         d.sg.dst = -1;
         return;
@@ -457,7 +468,9 @@ __device__ __forceinline__ uint32_t tap_off(uint32_t e) { return (e >> 13) & 0x3
 // instances: two 8-byte loads per staging group, one 16-bit chroma store per quad).  kPfRuntime: the launch's
 // `pix` (kPixInNv12 | kPixOutNv12), wave-uniform branches: mixed layouts and the colder mapper kinds.
 constexpr int kPfPlanar = 0, kPfNv12 = 3, kPfRuntime = 4;
-template <bool DWORD_STAGE, int MODE, bool VIG, bool TEX, int LG, bool E24, int PF = kPfPlanar>
+// EP: the instance of a LUT with quad-packed items (TiledLut::n_packed > 0: the blend = 0 mapper's LUT of the default
+// sampling, 32-bit entries; MODE 1 reads it for that mapper's scaled output and preview)
+template <bool DWORD_STAGE, int MODE, bool VIG, bool TEX, int LG, bool E24, int PF = kPfPlanar, bool EP = false>
 __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& frames, TiledLut lut, int W, int H, int use_gain,
                                                   int64_t out_pitch, RgbaOut rgba, int pix = 0) {
     constexpr int IN = PF == kPfRuntime ? kInRuntime : PF == kPfNv12 ? kInNv12 : kInPlanar;
@@ -470,6 +483,7 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
     // per frame and camera, (frame << cam_log2) + camera: in the dynamic region after the weight table
     float* const s_gain = reinterpret_cast<float*>(s_wtab + 1024);
     constexpr int lg = LG, cam_lg = LG <= 1 ? 5 : 4;  // frames per launch 1 << lg (FrameBatch)
+    static_assert(!EP || (!TEX && !E24), "quad records: the blend = 0 mapper's 32-bit LUT of the default sampling only");
     static_assert(MODE == 0 || LG == 0, "frame batches: MODE 0 only");
     // {g, g} per slot (finish_quad2f).  Written after an item's first barrier and read after its
     // second; the next write comes after the next item's first barrier, i.e. after every wave's last
@@ -529,7 +543,7 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
     const uint32_t g0 = group_issue(grsrc, t0, t_end, lg);
     __syncthreads();
     TileData d;
-    data_issue<DWORD_STAGE, VIG, E24, IN>(ersrc, cur, t_end, lg, stage_slot<true>(cur, t_end, wave), g0, d, in_nv12);
+    data_issue<DWORD_STAGE, VIG, E24, IN, EP>(ersrc, cur, t_end, lg, stage_slot<true>(cur, t_end, wave), g0, d, in_nv12);
     int t_mv = t0 + step < t_end ? t0 + step : t_end;  // item of the metadata in flight (mv)
     int t_n2 = t_mv < t_end && t0 + 2 * step < t_end ? t0 + 2 * step : t_end;  // item after it
     uint4 mv = meta_issue(mrsrc, t_mv, t_end, lg);
@@ -541,7 +555,7 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
     // so the compiler cannot fold them into one load at the header (waited on right there)
     asm volatile("" : "+v"(mv.x), "+v"(mv.y), "+v"(mv.z), "+v"(mv.w), "+v"(mg));
 #pragma unroll
-    for (int h = 0; h < kItemHalves; h++) {
+    for (int h = 0; h < (EP ? 1 : kItemHalves); h++) {
         asm volatile("" : "+v"(d.e4[h].x), "+v"(d.e4[h].y), "+v"(d.e4[h].z));
         if constexpr (!E24) asm volatile("" : "+v"(d.e4[h].w));
     }
@@ -570,7 +584,7 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
         const uint32_t S = cur.stride & ((1u << kStrideBits) - 1u);
         uint4 e4[kItemHalves];
 #pragma unroll
-        for (int h = 0; h < kItemHalves; h++) e4[h] = d.e4[h];
+        for (int h = 0; h < (EP ? 1 : kItemHalves); h++) e4[h] = d.e4[h];
         // every wave has read the previous item's staging area
         __syncthreads();
         if (tid < kTileZeroDwords) s_rgb[tid] = 0u;  // black pixels read offset 0 of the region
@@ -633,7 +647,7 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
                 store_half<MODE, OUT>(of, ro, res_rgba, prev[h], pcam, pfl, h, px, py + h * kTileH, pin && py + h * kTileH < H);
         }
         // the next item's first staging slot resolved only now (short scalar live ranges), then its loads
-        data_issue<DWORD_STAGE, VIG, E24, IN>(ersrc, nxt, t_end, lg, stage_slot<true>(nxt, t_end, wave), mg, d, in_nv12);
+        data_issue<DWORD_STAGE, VIG, E24, IN, EP>(ersrc, nxt, t_end, lg, stage_slot<true>(nxt, t_end, wave), mg, d, in_nv12);
         mv = meta_issue(mrsrc, t_n2, t_end, lg);
         mg = group_issue(grsrc, t_n2, t_end, lg);
         t_mv = t_n2;
@@ -645,8 +659,9 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
             asm volatile("" : "+v"(zero));
             claim = __hip_atomic_fetch_add(q + zero, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-#pragma unroll
-        for (int h = 0; h < kItemHalves; h++) {
+        // one half of the item from LDS: the lane's quad of 4-byte entries, or (EP, kItemPacked) its quad record;
+        // each form ends in its own finish, so that only the half's four result dwords outlive the branch
+        auto half_entries = [&](int h) {
             // E24: the four 24-bit entries from the three dwords (two v_alignbit_b32, one shift)
             const uint32_t ent[4] = {e4[h].x, E24 ? __builtin_amdgcn_alignbit(e4[h].y, e4[h].x, 24u) : e4[h].y,
                                      E24 ? __builtin_amdgcn_alignbit(e4[h].z, e4[h].y, 16u) : e4[h].z,
@@ -677,6 +692,42 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
                 if (MODE == 1 && !E24 && (e & kEntryNoGain)) gain[p] = f32x2_t{1.0f, 1.0f};
             }
             prev[h] = finish_any<MODE>(rgb, gain);
+        };
+        auto half_records = [&](int h, uint32_t lo, uint32_t hi) {
+            float rgb[4][3];
+            f32x2_t gain[4];
+            const uint32_t base4 = quad_base4(hi);
+            const f32x2_t gq = *reinterpret_cast<const f32x2_t*>(reinterpret_cast<const uint8_t*>(s_slot_gain) + quad_gain_off(hi));
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                // base + 4 dx + 4 S dy: the pixel's two flag bits, one per 16-bit half, times {4, 4 S} scaled
+                const uint32_t off = __builtin_amdgcn_udot2(
+                    __builtin_bit_cast(u16x2_t, hi & quad_flag_mask(p)),
+                    __builtin_bit_cast(u16x2_t, (uint32_t)uniform((int)quad_flag_mul(p, S))), base4, false);
+                const uint8_t* r0 = reinterpret_cast<const uint8_t*>(s_rgb) + off;
+                const uint8_t* r1 = r0 + 4u * S;
+                const uint32_t c00 = reinterpret_cast<const uint32_t*>(r0)[0];
+                const uint32_t c01 = reinterpret_cast<const uint32_t*>(r0)[1];
+                const uint32_t c10 = reinterpret_cast<const uint32_t*>(r1)[0];
+                const uint32_t c11 = reinterpret_cast<const uint32_t*>(r1)[1];
+                bilerp_rgba_w(c00, c01, c10, c11, wtab_read(quad_fxy_view(p, lo, hi)), rgb[p]);
+                gain[p] = gq;
+            }
+            prev[h] = finish_any<MODE>(rgb, gain);
+        };
+        bool records = false;
+        if constexpr (EP) records = (cur.nslots & kItemPacked) != 0u;  // wave-uniform
+        if (records) {
+            half_records(0, e4[0].x, e4[0].y);
+            half_records(1, e4[0].z, e4[0].w);
+        } else {
+            half_entries(0);
+            if constexpr (EP) {  // an unpacked item among packed ones: its second half is loaded (and waited for) here
+                TileData dd;
+                entry_issue<E24, EP>(ersrc, cur, t_end, lg, 1, dd);
+                e4[1] = dd.e4[1];
+            }
+            half_entries(1);
         }
         px = x;
         py = y;
@@ -708,21 +759,21 @@ __device__ __forceinline__ void stitch_tiled_body(const FrameBatch<1 << LG>& fra
 }
 
 // PF: kPfPlanar or kPfNv12 (compiled in)
-template <bool DWORD_STAGE, int MODE, bool VIG, int LG, bool E24, int PF = kPfPlanar>
+template <bool DWORD_STAGE, int MODE, bool VIG, int LG, bool E24, int PF = kPfPlanar, bool EP = false>
 __global__ void __launch_bounds__(256, kStitchRegBlocks) __attribute__((amdgpu_num_sgpr(kStitchSgprs)))
 __attribute__((amdgpu_num_vgpr(kStitchVgprs))) stitch_tiled_kernel(FrameBatch<1 << LG> frames, TiledLut lut, int W, int H,
                                                                    int use_gain, int64_t out_pitch, RgbaOut rgba) {
-    stitch_tiled_body<DWORD_STAGE, MODE, VIG, false, LG, E24, PF>(frames, lut, W, H, use_gain, out_pitch, rgba);
+    stitch_tiled_body<DWORD_STAGE, MODE, VIG, false, LG, E24, PF, EP>(frames, lut, W, H, use_gain, out_pitch, rgba);
 }
 // The instance of every other launch with an NV12 side: the layouts from `pix` (kPfRuntime), byte-wise staging
 // (any alignment) and the vignette path (cameras without one stage with kStageNoVig), at the texture
 // instance's register budget.  No conversion pass either: the same kernel reads and writes the layouts itself.
-template <int MODE, bool TEX, int LG, bool E24>
+template <int MODE, bool TEX, int LG, bool E24, bool EP = false>
 __global__ void __launch_bounds__(256, kStitchTexRegBlocks) __attribute__((amdgpu_num_sgpr(kStitchSgprs)))
 __attribute__((amdgpu_num_vgpr(kStitchTexVgprs))) stitch_tiled_pix_kernel(FrameBatch<1 << LG> frames, TiledLut lut, int W,
                                                                           int H, int use_gain, int64_t out_pitch,
                                                                           RgbaOut rgba, int pix) {
-    stitch_tiled_body<false, MODE, true, TEX, LG, E24, kPfRuntime>(frames, lut, W, H, use_gain, out_pitch, rgba, pix);
+    stitch_tiled_body<false, MODE, true, TEX, LG, E24, kPfRuntime, EP>(frames, lut, W, H, use_gain, out_pitch, rgba, pix);
 }
 template <bool DWORD_STAGE, int MODE, bool VIG, int LG>
 __global__ void __launch_bounds__(256, kStitchTexRegBlocks) __attribute__((amdgpu_num_sgpr(kStitchSgprs)))
@@ -809,14 +860,14 @@ struct TiledLaunch {
 };
 
 // The kernel of an instance: the choice between the three __global__ wrappers, written once.
-template <bool DW, int MODE, bool V, bool TEX, int LG, bool E24, int PF>
+template <bool DW, int MODE, bool V, bool TEX, int LG, bool E24, int PF, bool EP>
 constexpr auto tiled_kernel() {
     if constexpr (PF == kPfRuntime)
-        return &stitch_tiled_pix_kernel<MODE, TEX, LG, E24>;
+        return &stitch_tiled_pix_kernel<MODE, TEX, LG, E24, EP>;
     else if constexpr (TEX)
         return &stitch_tiled_tex_kernel<DW, MODE, V, LG>;
     else
-        return &stitch_tiled_kernel<DW, MODE, V, LG, E24, PF>;
+        return &stitch_tiled_kernel<DW, MODE, V, LG, E24, PF, EP>;
 }
 
 // The weight table's address (wtab_read) assumes the dynamic LDS starts right after StitchLds: checked
@@ -844,10 +895,10 @@ static void frame_batch(const FrameSet* frames, const double* const* gains, uint
     }
 }
 
-template <bool DW, int MODE, bool V, bool TEX, int LG, bool E24, int PF>
+template <bool DW, int MODE, bool V, bool TEX, int LG, bool E24, int PF, bool EP>
 static hipError_t launch_tiled(const TiledLaunch& a) {
     static_assert(PF != kPfNv12 || !TEX, "compiled-in NV12: the default sampling's instances");
-    constexpr auto kernel = tiled_kernel<DW, MODE, V, TEX, LG, E24, PF>();
+    constexpr auto kernel = tiled_kernel<DW, MODE, V, TEX, LG, E24, PF, EP>();
     static const hipError_t lds_ok = stitch_lds_check(reinterpret_cast<const void*>(kernel));
     if (lds_ok != hipSuccess) return lds_ok;
     FrameBatch<1 << LG> fb;
@@ -872,39 +923,42 @@ static hipError_t launch_tiled(const TiledLaunch& a) {
 }
 
 // the batch's frame count: 1, 2 or 4 (blend 0), 1 (MODE 1)
-template <bool DW, int MODE, bool V, bool TEX, bool E24, int PF = kPfPlanar>
+template <bool DW, int MODE, bool V, bool TEX, bool E24, int PF = kPfPlanar, bool EP = false>
 static hipError_t launch_tiled_lg(const TiledLaunch& a) {
     if constexpr (MODE == 0) {
-        if (a.lg == 1) return launch_tiled<DW, MODE, V, TEX, 1, E24, PF>(a);
-        if (a.lg == 2) return launch_tiled<DW, MODE, V, TEX, 2, E24, PF>(a);
+        if (a.lg == 1) return launch_tiled<DW, MODE, V, TEX, 1, E24, PF, EP>(a);
+        if (a.lg == 2) return launch_tiled<DW, MODE, V, TEX, 2, E24, PF, EP>(a);
     }
     if (a.lg != 0) return hipErrorInvalidValue;
-    return launch_tiled<DW, MODE, V, TEX, 0, E24, PF>(a);
+    return launch_tiled<DW, MODE, V, TEX, 0, E24, PF, EP>(a);
 }
 
 // the instance for the frames' staging (dword loads, vignette) and the entries' convention
-template <int MODE, bool TEX, bool E24>
+template <int MODE, bool TEX, bool E24, bool EP = false>
 static hipError_t launch_tiled_vd(const TiledLaunch& a) {
     if (a.pix) {
         // NV12 in and out, default sampling, aligned frames without vignette, blend 0: the compiled-in instance;
         // every other launch with an NV12 side: the instance that takes the layouts from `pix`
         if constexpr (MODE == 0 && !TEX) {
             if (a.pix == (kPixInNv12 | kPixOutNv12) && a.dw && !a.vig)
-                return launch_tiled_lg<true, MODE, false, TEX, E24, kPfNv12>(a);
+                return launch_tiled_lg<true, MODE, false, TEX, E24, kPfNv12, EP>(a);
         }
-        return launch_tiled_lg<false, MODE, true, TEX, E24, kPfRuntime>(a);
+        return launch_tiled_lg<false, MODE, true, TEX, E24, kPfRuntime, EP>(a);
     }
-    if (a.dw && !a.vig) return launch_tiled_lg<true, MODE, false, TEX, E24>(a);
-    if (a.dw) return launch_tiled_lg<true, MODE, true, TEX, E24>(a);
-    if (!a.vig) return launch_tiled_lg<false, MODE, false, TEX, E24>(a);
-    return launch_tiled_lg<false, MODE, true, TEX, E24>(a);
+    if (a.dw && !a.vig) return launch_tiled_lg<true, MODE, false, TEX, E24, kPfPlanar, EP>(a);
+    if (a.dw) return launch_tiled_lg<true, MODE, true, TEX, E24, kPfPlanar, EP>(a);
+    if (!a.vig) return launch_tiled_lg<false, MODE, false, TEX, E24, kPfPlanar, EP>(a);
+    return launch_tiled_lg<false, MODE, true, TEX, E24, kPfPlanar, EP>(a);
 }
 
-// the entries' width: 24-bit (TiledLut::e24, default sampling only) or 32-bit
+// the entries' width: 24-bit (TiledLut::e24, default sampling only) or 32-bit, the latter with quad-packed
+// items (TiledLut::n_packed: the blend = 0 mapper's LUT) or without
 template <int MODE, bool TEX>
 static hipError_t launch_tiled_for(const TiledLaunch& a) {
+    if (a.lut.n_packed > 0 && (TEX || a.lut.e24)) return hipErrorInvalidValue;
     if constexpr (!TEX) {
         if (a.lut.e24) return launch_tiled_vd<MODE, TEX, true>(a);
+        if (a.lut.n_packed > 0) return launch_tiled_vd<MODE, TEX, false, true>(a);
     } else {
         if (a.lut.e24) return hipErrorInvalidValue;  // texture-convention entries are never packed
     }

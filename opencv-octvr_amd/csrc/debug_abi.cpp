@@ -198,6 +198,18 @@ int octvr_debug_tiled_lut_info(const octvr_rig* rig, int n_inputs, const int* in
     });
 }
 
+int octvr_debug_entry_pack(const uint32_t* entries, int n_quads, uint32_t stride, uint64_t* records, uint8_t* ok,
+                           uint32_t* unpacked) {
+    return guarded([&] {
+        REQUIRE(entries && records && ok && unpacked && n_quads >= 0, "bad arguments");
+        REQUIRE(stride < (1u << kStrideBits), "stride exceeds its header field");
+        for (int q = 0; q < n_quads; q++) {
+            ok[q] = quad_pack(entries + 4 * (size_t)q, stride, &records[q]) ? 1 : 0;
+            quad_unpack(records[q], stride, unpacked + 4 * (size_t)q);
+        }
+    });
+}
+
 int octvr_debug_json_number(const char* json, int flags, double* value) {
     return guarded([&] {
         REQUIRE(json && value, "NULL argument");

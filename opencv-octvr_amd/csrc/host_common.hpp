@@ -199,6 +199,8 @@ struct TiledLutBuild {
     double staged_bytes = 0;  // YUV bytes staged, summed over items (groups of neighbouring items overlap)
     double source_bytes = 0;  // unique source bytes: the union of the staged groups (+ wide tiles' taps)
     std::string stats;  // JSON fragment: staged items by staging chunks / LDS bytes, per-band chunk sums
+    std::vector<uint8_t> packable;  // per staged item: every quad qualifies for the quad records (kernels.hpp quad_pack)
+    int n_packable = 0;
 };
 TiledLutBuild build_tiled_lut(const std::vector<TileJob>& jobs, const EntryFn& entry, const std::vector<int>& in_w,
                               const std::vector<int>& in_h, int qpl = 1);
@@ -218,7 +220,9 @@ struct TiledLutDev {
     std::string stats;
     TiledLut view{};
     // e24: pack the entries to 24 bits when no entry carries "no gain" (tiled_entry24)
-    void upload(const TiledLutBuild& b, bool e24 = false);
+    // quad: 8-byte quad records for the items that qualify (kItemPacked; the blend = 0 composite's LUT only)
+    void upload(const TiledLutBuild& b, bool e24 = false, bool quad = false);
+    int n_packed = 0;  // items uploaded as quad records
 };
 
 // ---- source footprint: the input bytes a mapper's kernels may read (tiling.cpp) ------------------------

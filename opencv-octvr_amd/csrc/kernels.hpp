@@ -306,6 +306,7 @@ struct TiledLut {
     uint32_t n_grp1;              // entries of grp1
     int tex;                      // staged entries are texture-convention ones (tiled_entry_tex)
     int e24;                      // entries packed to 24 bits (tiled_entry24): 12 bytes per lane and half
+    int n_packed;                 // items held as quad records (kItemPacked); > 0 selects the instances that read them
 };
 constexpr int kMetaWords = 1 + kTileSlots;
 constexpr int kQueueStride = 32;  // u32 words: one 128-B line per counter
@@ -333,6 +334,86 @@ __host__ __device__ constexpr uint32_t tiled_entry(uint32_t off, uint32_t fxy, u
 // three dwords (c0 | c1 << 24, c1 >> 8 | c2 << 16, c2 >> 16 | c3 << 8): 3 instead of 4 bytes per pixel.
 __host__ __device__ constexpr uint32_t tiled_entry24(uint32_t e) {
     return (e >> 30) | ((e >> 3) & 1023u) << 2 | ((e >> 15) & 4095u) << 12;
+}
+
+// Quad-packed items (blend = 0, default sampling): one 8-byte record per lane quad and half instead of four
+// 4-byte entries, for items whose every quad is either black (four entries 0: record 0) or has one slot, no
+// "no gain" pixel and tap origins within {0, 1} x {0, 1} of a common base (dword offsets base + dx + dy S,
+// S the item's row stride) — what an output that oversamples its sources produces away from seams.  Such an
+// item carries kItemPacked in TileHdr::nslots and keeps its records in the first half of its 8 KiB of
+// entries (lane quad q's records of half 0 and half 1 at byte 16 q: one 16-byte load per lane); any other item
+// keeps the 4-byte entries.
+//   lo: bits 2-11 fxy of pixel 0, 12-21 of pixel 1, 22-31 of pixel 2 (bits 0-1 zero)
+//   hi: bits 0-2 dx of pixels 0-2, 3 dy of pixel 3, 4-15 base, 16 dx of pixel 3, 17-19 dy of pixels 0-2,
+//       20-21 the slot, 22-31 fxy of pixel 3
+// Decode: pixel p's flags are one bit in each 16-bit half of hi & quad_flag_mask(p), so one v_dot2_u32_u16
+// with the item-uniform pair quad_flag_mul(p, S) adds 4 dx + 4 S dy to the base's byte offset; a shift puts
+// the pixel's fxy where wtab_read masks it (bits 3-12); the slot's gain is read once per quad.
+constexpr uint32_t kItemPacked = 1u << 24;  // TileHdr::nslots
+__host__ __device__ constexpr uint32_t quad_flag_mask(int p) {
+    return p == 3 ? (1u << 16 | 1u << 3) : (1u << p | 1u << (17 + p));
+}
+// the multipliers of the low and the high half's flag bit (S a multiple of 4 dwords, so every one is whole)
+__host__ __device__ constexpr uint32_t quad_flag_mul(int p, uint32_t S) {
+    return p == 3 ? ((S >> 1) | 4u << 16) : ((4u >> p) | ((2u * S) >> p) << 16);
+}
+// the record's dword (lo for pixels 0-2, hi for pixel 3) shifted so that fxy sits at bits 3-12
+__host__ __device__ constexpr uint32_t quad_fxy_view(int p, uint32_t lo, uint32_t hi) {
+    return p == 0 ? lo << 1 : p == 1 ? lo >> 9 : p == 2 ? lo >> 19 : hi >> 19;
+}
+// LDS byte offset of the base tap and of the slot's gain pair
+__host__ __device__ constexpr uint32_t quad_base4(uint32_t hi) { return (hi >> 2) & 0x3FFCu; }
+__host__ __device__ constexpr uint32_t quad_gain_off(uint32_t hi) { return (hi >> 17) & 0x18u; }
+
+// The four 4-byte entries of a record, by the arithmetic the kernel's decode runs (host model and tests).
+__host__ __device__ inline void quad_unpack(uint64_t rec, uint32_t S, uint32_t e[4]) {
+    const uint32_t lo = (uint32_t)rec, hi = (uint32_t)(rec >> 32);
+    for (int p = 0; p < 4; p++) {
+        if (!rec) {
+            e[p] = 0u;
+            continue;
+        }
+        const uint32_t a = hi & quad_flag_mask(p), m = quad_flag_mul(p, S);
+        const uint32_t off = quad_base4(hi) + (a & 0xFFFFu) * (m & 0xFFFFu) + (a >> 16) * (m >> 16);
+        e[p] = (quad_fxy_view(p, lo, hi) & 0x1FF8u) | off << 13 | (quad_gain_off(hi) >> 3) << 30;
+    }
+}
+
+// Packs a quad's four entries of an item of row stride S (dwords); false if the quad does not qualify.
+__host__ __device__ inline bool quad_pack(const uint32_t e[4], uint32_t S, uint64_t* rec) {
+    *rec = 0;
+    if (!(e[0] | e[1] | e[2] | e[3])) return true;  // black
+    if (S < 8u || (S & 3u)) return false;
+    uint32_t o[4], lo_o = 0xFFFFFFFFu;
+    for (int p = 0; p < 4; p++) {
+        // a black pixel beside live ones, a "no gain" pixel, a second slot
+        if (!e[p] || (e[p] & 7u) || (e[p] >> 27 & 7u) || (e[p] >> 30) != (e[0] >> 30)) return false;
+        if ((e[p] >> 13) & 3u) return false;
+        o[p] = ((e[p] >> 13) & 0x3FFFu) >> 2;
+        lo_o = o[p] < lo_o ? o[p] : lo_o;
+    }
+    // the base: the lowest origin, or the dword before it when the quad's leftmost and topmost origins differ
+    // (origins at (1, 0) and (0, 1) of the cell)
+    for (uint32_t back = 0; back < 2; back++) {
+        if (lo_o < back) break;
+        const uint32_t base = lo_o - back;
+        uint32_t dx[4], dy[4];
+        bool ok = true;
+        for (int p = 0; p < 4 && ok; p++) {
+            const uint32_t d = o[p] - base;
+            ok = d == 0u || d == 1u || d == S || d == S + 1u;
+            dx[p] = (d == 1u || d == S + 1u) ? 1u : 0u;
+            dy[p] = d >= S ? 1u : 0u;
+        }
+        if (!ok) continue;
+        const uint32_t f[4] = {(e[0] >> 3) & 1023u, (e[1] >> 3) & 1023u, (e[2] >> 3) & 1023u, (e[3] >> 3) & 1023u};
+        const uint32_t lo = f[0] << 2 | f[1] << 12 | f[2] << 22;
+        const uint32_t hi = dx[0] | dx[1] << 1 | dx[2] << 2 | dy[3] << 3 | base << 4 | dx[3] << 16 | dy[0] << 17 |
+                            dy[1] << 18 | dy[2] << 19 | (e[0] >> 30) << 20 | f[3] << 22;
+        *rec = (uint64_t)hi << 32 | lo;
+        return true;
+    }
+    return false;
 }
 
 // A staged texture-convention pixel (make_entry_tex with all four taps inside the image): bit 0 "no gain",

@@ -404,7 +404,7 @@ std::unique_ptr<octvr_mapper> mapper_create(const octvr_rig* rig, int device, in
         const std::vector<CompositeEntry> lut8 = winner_lut(*m, camera, 0, m->nc);
         const TiledLutBuild tb = build_frame_tiles(lut8, m->W, m->H, m->in_w, m->in_h, &m->n_tiles);
         footprint_add_tiles(m->foot, tb);
-        m->tiles.upload(tb);
+        m->tiles.upload(tb, false, true);  // quad records for the items that qualify
     }
     if (m->mb && n_ov) setup_overlays(*m, camera);
     if (m->scaled || m->ov.view.n_groups) ensure_result(*m);
@@ -477,10 +477,10 @@ int mapper_drain_timing(octvr_mapper* m, const std::function<void(double, double
     return launches;
 }
 
-// The bytes of the tiled LUT one pass of the composite reads: 4 B entries (3 B packed, 8 B in wide tiles),
-// tile headers / slots.
-double tiled_lut_bytes(const TiledLut& t) {
-    return (t.e24 ? 3.0 : 4.0) * t.n_items * kTilePx * t.qpl + 8.0 * t.n_wide * kTilePx +
+// The bytes of the tiled LUT one pass of the composite reads: 4 B entries (3 B packed, 2 B in the n_packed
+// items of quad records, 8 B in wide tiles), tile headers / slots.
+double tiled_lut_bytes(const TiledLut& t, int n_packed) {
+    return (t.e24 ? 3.0 : 4.0) * t.n_items * kTilePx * t.qpl - 2.0 * n_packed * kTilePx * t.qpl + 8.0 * t.n_wide * kTilePx +
            (double)t.n_items * (sizeof(TileHdr) + kTileSlots * sizeof(TileSlot)) + 4.0 * t.n_wide;
 }
 
@@ -496,7 +496,7 @@ double mapper_traffic(const octvr_mapper* m) {
         return multiband_traffic(*m->mb) + 4.0 * m->W * m->H + 1.5 * m->SW * m->SH +
                (double)m->ov.view.n_groups * (4.0 + 8.0 * kOvGroupPx) + m->ov.source_bytes + 4.0 * (double)m->ov.covered;
     if (m->mb) return multiband_traffic(*m->mb);
-    return tiled_lut_bytes(m->tiles.view) + 1.5 * m->W * m->H + m->tiles.source_bytes;
+    return tiled_lut_bytes(m->tiles.view, m->tiles.n_packed) + 1.5 * m->W * m->H + m->tiles.source_bytes;
 }
 
 }  // namespace octvr

@@ -109,7 +109,7 @@ void mapper_set_timing(octvr_mapper* m, int enable);
 int mapper_drain_timing(octvr_mapper* m, const std::function<void(double start_ms, double end_ms)>& f);
 // Algorithmic bytes of one frame, and the part of them a batch reads once (the tiled LUT).
 double mapper_traffic(const octvr_mapper* m);
-double tiled_lut_bytes(const TiledLut& t);
+double tiled_lut_bytes(const TiledLut& t, int n_packed = 0);
 // The per-frame composite's tiled LUT of a W x H winner LUT: items of 128 x (8 composite_qpl()) pixels,
 // black outside the frame.  n_jobs: the items of the grid, empty ones included.
 TiledLutBuild build_frame_tiles(const std::vector<CompositeEntry>& lut, int W, int H, const std::vector<int>& in_w,

@@ -405,7 +405,7 @@ int octvr_mapper_traffic_parts(const octvr_mapper* m, double* lut_bytes, double*
     return guarded([&] {
         REQUIRE(m && lut_bytes && frame_bytes, "NULL argument");
         // multi-band has no batched kernels: everything is per frame
-        *lut_bytes = m->mb ? 0.0 : tiled_lut_bytes(m->tiles.view);
+        *lut_bytes = m->mb ? 0.0 : tiled_lut_bytes(m->tiles.view, m->tiles.n_packed);
         *frame_bytes = mapper_traffic(m) - *lut_bytes;
     });
 }
@@ -498,7 +498,7 @@ int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
                  m->foot.bytes(), m->nc - m->n, m->ov.view.n_groups, m->ov.covered);
         std::string js = tmp;
         if (m->mb) js += ", " + multiband_info(*m->mb);
-        else if (!m->tiles.stats.empty()) js += ", " + m->tiles.stats;
+        else if (!m->tiles.stats.empty()) js += ", " + m->tiles.stats + ", \"items_packed\": " + std::to_string(m->tiles.n_packed);
         js += "}";
         REQUIRE(js.size() < len, "buffer too small");
         memcpy(buf, js.c_str(), js.size() + 1);

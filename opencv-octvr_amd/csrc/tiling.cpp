@@ -7,6 +7,9 @@
 // builder finds the cameras (<= 4 "slots") and their even-aligned luma boxes, and encodes each
 // pixel as a 4-byte box-relative LDS byte offset + fractions + slot; jobs that do not
 // fit (> 4 cameras, a box > 256 px, or LDS above kTileLdsBytes) become "wide" with 8-byte entries.
+// Staged items whose every lane quad has one slot and tap origins within one source cell of each other are
+// counted as packable, and the blend = 0 composite's upload stores them as 8-byte quad records (kernels.hpp
+// kItemPacked): half the entry bytes where the output oversamples its sources.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -18,6 +21,14 @@
 #include "kernels.hpp"
 
 namespace octvr {
+
+// every quad of a staged item's entries (row stride S) packs (kernels.hpp quad_pack)
+static bool item_packable(const uint32_t* E, int item_px, uint32_t S) {
+    uint64_t rec;
+    for (int k = 0; k < item_px; k += 4)
+        if (!quad_pack(E + k, S, &rec)) return false;
+    return true;
+}
 
 TiledLutBuild build_tiled_lut(const std::vector<TileJob>& jobs, const EntryFn& entry, const std::vector<int>& in_w,
                               const std::vector<int>& in_h, int qpl) {
@@ -386,6 +397,14 @@ TiledLutBuild build_tiled_lut(const std::vector<TileJob>& jobs, const EntryFn& e
         s += "], \"band_chunks\": [";
         for (int g = 0; g < kStitchBands; g++) s += (g ? ", " : "") + std::to_string(band_chunks[g]);
         s += "]";
+        // items every quad of which qualifies for the 8-byte quad records (default sampling only)
+        b.packable.assign((size_t)std::max(n_items, 1), 0);
+        for (int t = 0; t < n_items && !b.tex; t++) {
+            b.packable[t] = item_packable(b.entries.data() + (size_t)t * kTilePx * qpl, kTilePx * qpl,
+                                          b.hdr[t].stride & ((1u << kStrideBits) - 1u)) ? 1 : 0;
+            b.n_packable += b.packable[t];
+        }
+        s += ", \"items_packable\": " + std::to_string(b.n_packable);
         b.stats = s;
     }
     b.hdr.resize(std::max(n_items, 1));
@@ -401,11 +420,26 @@ TiledLutBuild build_tiled_lut(const std::vector<TileJob>& jobs, const EntryFn& e
     return b;
 }
 
-void TiledLutDev::upload(const TiledLutBuild& b, bool want_e24) {
+// Quad records at mapper creation: by default (kQuadPackDefault) where more than half of the items qualify (the
+// instances that read records load an unpacked item's second half late); OCTVR_ENTRY_QUAD=0 or OCTVR_ENTRY32
+// keeps every item's 4-byte entries, OCTVR_ENTRY_QUAD=1 packs whatever qualifies (A/B runs, tests)
+constexpr bool kQuadPackDefault = true;
+static bool quad_pack_wanted(int n_packable, int n_items) {
+    if (std::getenv("OCTVR_ENTRY32")) return false;
+    const char* v = std::getenv("OCTVR_ENTRY_QUAD");
+    if (v && *v) return std::strcmp(v, "0") != 0;
+    return kQuadPackDefault && 2 * n_packable > n_items;
+}
+
+void TiledLutDev::upload(const TiledLutBuild& b, bool want_e24, bool want_quad) {
     // per staged item one 80-byte record: its TileHdr, then its kTileSlots TileSlots (lane q of the
     // metadata load reads 16-byte word q)
     static_assert(sizeof(TileHdr) == 16 && sizeof(TileSlot) == 16, "16-byte metadata words");
     std::vector<TileHdr> m(b.hdr.size() * kMetaWords);
+    // quad records (kernels.hpp kItemPacked) where asked for (the blend = 0 composite of the default sampling)
+    const bool quad = want_quad && !want_e24 && !b.tex && b.qpl == kItemHalves && b.n_packable > 0 &&
+                      quad_pack_wanted(b.n_packable, b.n_items);
+    n_packed = 0;
     for (size_t t = 0; t < b.hdr.size(); t++) {
         m[t * kMetaWords] = b.hdr[t];
         // word 2 on the device: the slot of each staging chunk c < 4 (2 bits at 2c), as stage_slot's
@@ -419,6 +453,7 @@ void TiledLutDev::upload(const TiledLutBuild& b, bool want_e24) {
         }
         if (t < b.item_flags.size()) map |= (uint32_t)b.item_flags[t] << 8;  // RGBA mode: item_result_bit / item_g0_bit
         m[t * kMetaWords].stage_groups = map;
+        if (quad && t < b.packable.size() && t < (size_t)b.n_items && b.packable[t]) m[t * kMetaWords].nslots |= kItemPacked;
         std::memcpy(&m[t * kMetaWords + 1], &b.slots[t * kTileSlots], kTileSlots * sizeof(TileSlot));
     }
     meta.upload(m.data(), m.size());
@@ -442,6 +477,25 @@ void TiledLutDev::upload(const TiledLutBuild& b, bool want_e24) {
             p[3 * q] = c0 | c1 << 24;
             p[3 * q + 1] = c1 >> 8 | c2 << 16;
             p[3 * q + 2] = c2 >> 16 | c3 << 8;
+        }
+        entries.upload(p.data(), p.size());
+    } else if (quad && b.n_packable > 0) {
+        // a packed item's records in the first half of its entries (lane quad q's two halves at byte 16 q), the rest zero
+        std::vector<uint32_t> p(b.entries);
+        const size_t item_px = (size_t)kTilePx * b.qpl;
+        for (int t = 0; t < b.n_items; t++) {
+            if (!b.packable[t]) continue;
+            uint32_t* E = p.data() + (size_t)t * item_px;
+            const uint32_t S = b.hdr[t].stride & ((1u << kStrideBits) - 1u);
+            for (size_t k = 0; k < item_px; k += 4) {
+                uint64_t rec = 0;
+                REQUIRE(quad_pack(b.entries.data() + (size_t)t * item_px + k, S, &rec), "tiled LUT: quad record (internal error)");
+                const size_t h = k / kTilePx, q = (k % kTilePx) / 4;
+                E[q * 4 + h * 2] = (uint32_t)rec;
+                E[q * 4 + h * 2 + 1] = (uint32_t)(rec >> 32);
+            }
+            std::fill(E + kTilePx, E + item_px, 0u);
+            n_packed++;
         }
         entries.upload(p.data(), p.size());
     } else {
@@ -471,7 +525,7 @@ void TiledLutDev::upload(const TiledLutBuild& b, bool want_e24) {
     if (b.item_flags.empty()) g0_bytes = 4.0 * kTilePx * ((double)b.n_items * b.qpl + b.n_wide);  // no flags: every half
     stats = b.stats;
     view = TiledLut{meta.p, entries.p, b.n_items, wide_tiles.p, wide.p, b.n_wide, wide_cams.p, bands.p, queue.p,
-                    b.qpl, grp0.p, grp1.p, (uint32_t)b.grp1.size(), b.tex, e24 ? 1 : 0};
+                    b.qpl, grp0.p, grp1.p, (uint32_t)b.grp1.size(), b.tex, e24 ? 1 : 0, n_packed};
 }
 
 void SourceFootprint::init(const std::vector<int>& in_w, const std::vector<int>& in_h) {

@@ -145,6 +145,8 @@ if hasattr(_lib, "octvr_debug_json_number"):
 if hasattr(_lib, "octvr_debug_tiled_lut_info"):
     _lib.octvr_debug_tiled_lut_info.argtypes = [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
                                                 C.c_char_p, C.c_size_t]
+if hasattr(_lib, "octvr_debug_entry_pack"):
+    _lib.octvr_debug_entry_pack.argtypes = [_VP, C.c_int, C.c_uint32, _VP, _VP, _VP]
 if hasattr(_lib, "octvr_debug_fastmapper_audit"):
     _lib.octvr_debug_fastmapper_audit.argtypes = [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
                                                   C.c_int, C.c_char_p, C.c_size_t]
@@ -192,6 +194,21 @@ def debug_tiled_lut_info(mt, in_sizes, remap="remap"):
     _check(_lib.octvr_debug_tiled_lut_info(mt._h, n, w, h, REMAP_TEXTURE if remap == "texture" else 0, buf, len(buf)))
     import json as _json
     return _json.loads(buf.value.decode())
+
+
+def debug_entry_pack(entries, stride):
+    """(ok, records, unpacked) of quads of four 4-byte tiled entries (an (n, 4) uint32 array) of an item of LDS
+    row stride `stride`: whether each quad qualifies for an 8-byte quad record, the record, and the entries
+    it decodes back to (octvr_debug_entry_pack; no GPU)."""
+    import numpy as _np
+    e = _np.ascontiguousarray(entries, _np.uint32).reshape(-1, 4)
+    n = e.shape[0]
+    rec = _np.zeros(n, _np.uint64)
+    ok = _np.zeros(n, _np.uint8)
+    un = _np.zeros((n, 4), _np.uint32)
+    _check(_lib.octvr_debug_entry_pack(e.ctypes.data_as(_VP), n, int(stride), rec.ctypes.data_as(_VP),
+                                       ok.ctypes.data_as(_VP), un.ctypes.data_as(_VP)))
+    return ok.astype(bool), rec, un
 
 
 def _plane_args(plane_sets):
