@@ -482,6 +482,9 @@ public:
         m_ = std::shared_ptr<octvr_mapper>(m, [](octvr_mapper* p) { octvr_mapper_destroy(p); });
         out_ = scale_output.width > 0 ? scale_output : mt.out_size;
         sizes_ = in_sizes;
+        // a blend-0 mapper (a single input disables the blend, mapper.cpp:78-82) with the output at template
+        // size can preview without the result frame (octvr_mapper_prepare_preview)
+        gather_preview_ = (blend == 0 || n_gains_ <= 1) && out_ == mt.out_size;
     }
     // inputs and output are YUV420P GpuMats (CV_8U, 3H/2 rows) in the layout of mapper.hpp:75-83;
     // preview_output (CV_8UC3, optional) receives the RGB result resized (mapper.cpp:308-312).
@@ -504,6 +507,13 @@ public:
         const double* g = gains.empty() ? nullptr : gains.data();
         if (!preview_output.empty()) {
             if (preview_output.type() != CV_8UC3) throw cv::Exception(OCTVR_E_INVALID, "preview_output must be CV_8UC3");
+            // the preview's size comes with the GpuMat: prepared on the first one and again when it changes
+            const cv::Size ps(preview_output.cols, preview_output.rows);
+            if (gather_preview_ && ps != prepared_ &&
+                (int64_t)ps.width * ps.height <= (int64_t)OCTVR_MAX_PREPARED_PREVIEW_PIXELS) {
+                detail::check(octvr_mapper_prepare_preview(m_.get(), rig_.get(), ps.width, ps.height));
+                prepared_ = ps;
+            }
             detail::check(octvr_mapper_stitch_preview(m_.get(), p.data(), pitch.data(), output.data, output.step,
                                                       preview_output.data, preview_output.cols, preview_output.rows,
                                                       preview_output.step, g, (int)gains.size(), nullptr));
@@ -538,6 +548,8 @@ private:
     int n_ = 0, n_gains_ = 0;
     cv::Size out_;
     std::vector<cv::Size> sizes_;
+    bool gather_preview_ = false;
+    cv::Size prepared_;  // the preview size the mapper is prepared for (0 x 0: none yet)
 };
 
 struct PreviewDataHeader {

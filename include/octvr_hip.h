@@ -191,10 +191,31 @@ int octvr_mapper_stitch_batch(octvr_mapper* mapper, int n_frames, const uint8_t*
                               uint8_t* const* out_dev, size_t out_pitch, const double* gains, void* stream);
 /* The same with Mapper::stitch's preview_output (mapper.cpp:308-312): the RGB result resized
  * (cuda::resize INTER_LINEAR) into a preview_w x preview_h CV_8UC3 device image (3 bytes per pixel,
- * row pitch preview_pitch); preview_dev NULL = none.  Needs one frame in flight. */
+ * row pitch preview_pitch); preview_dev NULL = none.  Needs one frame in flight, unless preview_w x preview_h is
+ * the size octvr_mapper_prepare_preview prepared: then the stitch is the one without a preview and the preview
+ * is gathered after it (below). */
 int octvr_mapper_stitch_preview(octvr_mapper* mapper, const uint8_t* const* in_dev, const size_t* in_pitch,
                                 uint8_t* out_dev, size_t out_pitch, uint8_t* preview_dev, int preview_w, int preview_h,
                                 size_t preview_pitch, const double* gains, int n_gains, void* stream);
+/* A preview without the result frame (no reference counterpart), for a blend-0 mapper with the output at
+ * template size.  There a result pixel is a function of one camera's four taps and that camera's gain, so the
+ * preview's pixels can be computed from the source frames: this call builds, for exactly preview_w x preview_h,
+ * the list of the result pixels cuda::resize INTER_LINEAR reads (four per preview pixel, 32 bytes of device memory
+ * per preview pixel) from `rig`.  Afterwards octvr_mapper_stitch_preview with a preview of that size runs the
+ * launches of a stitch without a preview plus one gather kernel on the same stream: the same bytes as the
+ * result-frame path, the result frame never allocated, any number of frames in flight, the timed interval
+ * (octvr_mapper_set_timing) covering the composite and the gather.  A preview of any other size takes the
+ * result-frame path as before, with its one frame in flight.  One prepared size per mapper: a second call
+ * replaces it, 0, 0 drops it.  `rig` must be the rig the mapper was created from (the mapper keeps no maps): a rig
+ * whose output size, input count, overlay count or ROIs differ is OCTVR_E_INVALID; the same maps are the
+ * caller's contract.  Overlays of a blend-0 mapper are cameras of the same LUT and are covered.
+ * OCTVR_E_UNSUPPORTED (the reason in octvr_last_error) for a multi-band / feather mapper, whose result is not
+ * a per-pixel function of the sources, and for a scaled output, which needs the result frame anyway.
+ * Synchronizes the mapper, as octvr_mapper_set_frames_in_flight does.  octvr_mapper_info reports
+ * "preview_prepared": [w, h] ([0, 0]: none) and "preview_entries"; octvr_mapper_traffic models the stitch and
+ * does not change.  preview_w * preview_h <= OCTVR_MAX_PREPARED_PREVIEW_PIXELS (OCTVR_E_INVALID above). */
+#define OCTVR_MAX_PREPARED_PREVIEW_PIXELS (1 << 26)
+int octvr_mapper_prepare_preview(octvr_mapper* mapper, const octvr_rig* rig, int preview_w, int preview_h);
 /* Mapper::gains() (mapper.hpp:88-90): gains used by the last stitch, one per input (n >= N; overlays have
  * none) (synchronizes the stream). */
 int octvr_mapper_gains(octvr_mapper* mapper, double* gains, int n);
@@ -282,7 +303,9 @@ int octvr_async_create_ex(const octvr_rig* const* rigs, int n_rigs, int device, 
  * none), which is downloaded with the outputs and published when the frame's outputs are written:
  * octvr_async_pop_preview reads the latest, a sink receives every one.  preview_w = preview_h = 0: none
  * (= octvr_async_create_ex).  Mappers with a preview stitch through their RGB result frame
- * (mapper.cpp:266-312 order: composite, then RGB -> YUV420P and the preview resize). */
+ * (mapper.cpp:266-312 order: composite, then RGB -> YUV420P and the preview resize), except a blend-0 mapper
+ * whose region is at its template's size: that one is prepared for its preview rectangle's size
+ * (octvr_mapper_prepare_preview) and gathers the same bytes after its plain composite. */
 int octvr_async_create_preview(const octvr_rig* const* rigs, int n_rigs, int device, int n_inputs, const int* in_w,
                                const int* in_h, int out_w, int out_h, const int* blend_modes, const int* gain_modes,
                                const double* output_regions, int flags, int preview_w, int preview_h,
@@ -311,7 +334,8 @@ int octvr_async_set_preview_sink(octvr_async* async, octvr_preview_sink sink, vo
 /* Build-time facts of the pipeline as a JSON object: packed_bytes (the footprint bytes uploaded per frame,
  * run gaps included), runs, frame bytes, preview size, the mappers' creation flags, and "pixel_formats":
  * [in, out], the current OCTVR_PIX_* pair; "device_frames", the frames octvr_async_push_device has queued so
- * far, and "merge_launches", the merge kernel's launches for them (0 or 1 per device frame). */
+ * far, and "merge_launches", the merge kernel's launches for them (0 or 1 per device frame);
+ * "preview_prepared": per mapper the [w, h] of the preview it gathers from the source frames ([0, 0]: none). */
 int octvr_async_info(const octvr_async* async, char* buf, size_t len);
 /* Pixel layouts of the pipeline's host planes (no reference counterpart: the reference's planes are planar;
  * decoders, capture cards and encoders speak NV12): OCTVR_PIX_YUV420P (the default) or OCTVR_PIX_NV12, for the

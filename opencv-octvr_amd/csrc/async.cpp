@@ -640,6 +640,12 @@ int octvr_async_create_preview(const octvr_rig* const* rigs, int n_rigs, int dev
                                                   gain_modes[k] >= 0 ? 1 : 0, r.w, r.h, flags, &m);
             if (rc != OCTVR_OK) throw OctvrError(rc, std::string("mapper ") + std::to_string(k) + ": " + octvr_last_error());
             a->mappers.push_back(m);
+            // a blend-0 mapper whose region is at template size gathers its preview rectangle from the source
+            // frames (octvr_mapper_prepare_preview); every other mapper previews from its result frame
+            const Rect& pr = a->preview_rects.back();
+            if (pr.w > 0 && pr.h > 0 && !m->mb && !m->scaled &&
+                (uint64_t)pr.w * (uint64_t)pr.h <= (uint64_t)OCTVR_MAX_PREPARED_PREVIEW_PIXELS)
+                mapper_prepare_preview(m, rigs[k], pr.w, pr.h);
             // n_inputs = N_k + K_k held for this rig (mapper_create); the split may differ per rig, but a
             // chained mapper takes the other's N gains
             const int gm = gain_modes[k];
@@ -934,15 +940,23 @@ int octvr_async_info(const octvr_async* a, char* buf, size_t len) {
     snprintf(tmp, sizeof tmp,
              "{\"mappers\": %d, \"inputs\": %d, \"packed_bytes\": %zu, \"runs\": %zu, \"input_frame_bytes\": %zu, "
              "\"output_bytes\": %zu, \"preview\": [%d, %d], \"flags\": %d, \"slots\": %d, \"pixel_formats\": [%d, %d], "
-             "\"device_frames\": %lld, \"merge_launches\": %lld}",
+             "\"device_frames\": %lld, \"merge_launches\": %lld",
              (int)a->mappers.size(), a->n_in, a->packed_bytes, a->runs.size(), in_bytes, out_bytes, a->preview_w,
              a->preview_h, a->flags, kSlots, a->in_fmt, a->out_fmt, (long long)a->device_frames,
              (long long)a->merge_launches.load());
-    if (strlen(tmp) >= len) {
+    // per mapper the preview size it gathers from the source frames ([0, 0]: it previews from its result frame,
+    // or has no preview)
+    std::string js = tmp;
+    js += ", \"preview_prepared\": [";
+    for (size_t k = 0; k < a->mappers.size(); k++)
+        js += std::string(k ? ", [" : "[") + std::to_string(a->mappers[k]->pv.view.dw) + ", " +
+              std::to_string(a->mappers[k]->pv.view.dh) + "]";
+    js += "]}";
+    if (js.size() >= len) {
         set_last_error("buffer too small");
         return OCTVR_E_INVALID;
     }
-    memcpy(buf, tmp, strlen(tmp) + 1);
+    memcpy(buf, js.c_str(), js.size() + 1);
     return OCTVR_OK;
 }
 

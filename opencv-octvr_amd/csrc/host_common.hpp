@@ -256,6 +256,12 @@ struct OverlayListDev {
     OverlayList view{};
 };
 
+// ---- gathered preview of a blend-0 mapper: preview_gather_kernel's tap list on the device (mapper.cpp) ----
+struct PreviewListDev {
+    DevBuf<CompositeEntry> entries;
+    PreviewList view{};  // dw = dh = 0: nothing prepared
+};
+
 // ---- multi-band blend (multiband_host.cpp) ---------------------------------------------------------
 class MultiBand;
 struct MultiBandDeleter {

@@ -645,6 +645,25 @@ struct OverlayList {
 hipError_t launch_overlay_apply(const FrameSet& frames, const OverlayList& list, uint8_t* rgba, int64_t rgba_pitch,
                                 hipStream_t s, int pix = 0);
 
+// ---- gathered preview of a blend-0 mapper (preview.hip) -----------------------------------------
+// At blend 0 a result pixel is a function of one camera's four taps and that camera's gain, so the preview
+// (cuda::resize INTER_LINEAR of the result, mapper.cpp:308-312) needs no result frame: per preview pixel
+// the composite's 8-byte entries of the four result pixels the resize reads, (y1, x1), (y1, x2r), (y2r, x1),
+// (y2r, x2r), built once per preview size (preview_list.hpp), entry 4 pixel + tap in raster order.  An
+// entry with the valid bit clear (a result pixel no camera claims, the padding) evaluates to black.
+constexpr int kPvBlockEntries = 256;  // entries of one workgroup: 64 preview pixels, one tap per lane
+struct PreviewList {
+    const CompositeEntry* entries;
+    uint32_t n_entries;  // a multiple of kPvBlockEntries (padded with zero entries)
+    uint32_t n_pixels;   // dw * dh; 4 n_pixels <= n_entries
+    int32_t dw, dh;      // the preview size the list was built for
+    float fx, fy;        // resize_rgba_rgb_kernel's scales, (float)(1.0 / ((double)dw / W)) and the same for y
+};
+// out: the dw x dh CV_8UC3 preview, 3 bytes per pixel at out_pitch; gains: a frame slot's kMaxCams doubles.
+// pix: kPixInNv12 (the preview stays RGB)
+hipError_t launch_preview_gather(const FrameSet& frames, const PreviewList& list, const double* gains, int use_gain,
+                                 uint8_t* out, int64_t out_pitch, hipStream_t s, int pix = 0);
+
 hipError_t launch_selftest_sat(const float* in, uint8_t* out, int n, int method, hipStream_t s);
 
 }  // namespace octvr

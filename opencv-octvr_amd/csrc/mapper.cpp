@@ -2,6 +2,7 @@
 // timing read-back and the traffic model.  Host orchestration only; the kernels are in the *.hip files.
 #include "mapper.hpp"
 #include "overlay_list.hpp"
+#include "preview_list.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -212,12 +213,17 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
                    size_t out_pitch, const double* gains, int n_gains, const double* gains_dev, hipStream_t s,
                    const PreviewOut* preview) {
     REQUIRE(m && in_dev && in_pitch && out_dev, "NULL argument");
+    // a preview of the prepared size is gathered from the source frames after the composite (preview.hip):
+    // the stitch itself is the one without a preview
+    const bool gathered = preview && m->pv.view.dw > 0 && preview->w == m->pv.view.dw && preview->h == m->pv.view.dh;
     if (preview) {
         REQUIRE(preview->dev && preview->w > 0 && preview->h > 0 && preview->pitch >= (size_t)preview->w * 3,
                 "bad preview output");
-        // the preview resizes the whole-frame RGB result, which one frame slot owns
-        REQUIRE(m->slots.size() == 1, "preview output needs one frame in flight");
-        ensure_result(*m);
+        if (!gathered) {
+            // the preview resizes the whole-frame RGB result, which one frame slot owns
+            REQUIRE(m->slots.size() == 1, "preview output needs one frame in flight");
+            ensure_result(*m);
+        }
     }
     check_out_pitch(m, out_pitch);
     DeviceGuard dg(m->device);
@@ -231,7 +237,7 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
     // overlays after a blend are copied onto the RGB(A) result too (mapper.cpp:279-287)
     const bool overlays = m->ov.view.n_groups > 0;
     if (timed && (m->scaled || m->mb || preview)) HIP_CHECK(hipEventRecord(e0, s));  // else the composite records its own
-    if (m->scaled || preview || overlays) {
+    if (m->scaled || (preview && !gathered) || overlays) {
         // stitch at template size into the RGB(A) result, then resize + RGB -> YUV420P (mapper.cpp:290-306)
         // (one frame slot only: the result frame is shared); without scaling the resize is the identity
         if (m->mb)
@@ -250,8 +256,12 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
     } else {
         TiledLut view = m->tiles.view;
         view.queue = sl.queue;
-        HIP_CHECK(launch_stitch(fs, view, m->W, m->H, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s, e0, e1,
-                                m->pix));
+        // with a gathered preview the events above and below bracket the composite and the preview kernel
+        HIP_CHECK(launch_stitch(fs, view, m->W, m->H, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s,
+                                gathered ? nullptr : e0, gathered ? nullptr : e1, m->pix));
+        if (gathered)
+            HIP_CHECK(launch_preview_gather(fs, m->pv.view, sl.gains, m->use_gain, preview->dev, (int64_t)preview->pitch, s,
+                                            m->pix));
     }
     if (timed && (m->scaled || m->mb || preview)) HIP_CHECK(hipEventRecord(e1, s));
     ev.keep();
@@ -384,6 +394,7 @@ std::unique_ptr<octvr_mapper> mapper_create(const octvr_rig* rig, int device, in
     m->vig.resize(m->nc);
     for (int i = 0; i < m->nc; i++) {
         const RigInput& in = camera(i);
+        m->rois.insert(m->rois.end(), in.roi, in.roi + 4);
         if (in.vignette.empty()) continue;
         const std::vector<float> v = resize_linear_f32(in.vignette.data(), in.vig_w, in.vig_h, m->in_w[i], m->in_h[i]);
         m->vig[i].upload(v.data(), v.size());
@@ -440,6 +451,49 @@ void mapper_set_frames_in_flight(octvr_mapper* m, int k) {
     for (int i = 1; i < k; i++) m->slots.push_back(make_slot(*m));
     if (m->mb) multiband_set_slots(*m->mb, k);
     HIP_CHECK(hipDeviceSynchronize());  // the memsets complete before any stream uses the slots
+}
+
+void mapper_prepare_preview(octvr_mapper* m, const octvr_rig* rig, int w, int h) {
+    REQUIRE(m && w >= 0 && h >= 0 && (w == 0) == (h == 0), "bad arguments");
+    // the blender's result is not a function of one camera's taps, and a scaled mapper stitches through the
+    // result frame whatever its preview
+    if (m->mb)
+        throw OctvrError(OCTVR_E_UNSUPPORTED, "a prepared preview needs blend 0: a blended pixel is not a function of one "
+                                              "camera's taps (multi-band / feather mappers preview from the result frame)");
+    if (m->scaled)
+        throw OctvrError(OCTVR_E_UNSUPPORTED, "a prepared preview needs the output at template size: a scaled mapper "
+                                              "stitches through the result frame anyway");
+    DeviceGuard dg(m->device);
+    mapper_sync(*m);  // stitches in flight read the list they were issued with
+    if (w == 0) {
+        m->pv.entries.reset();
+        m->pv.view = PreviewList{};
+        return;
+    }
+    // 4 entries per pixel: the entry index stays below 2^28 and the list below 2 GiB
+    REQUIRE((uint64_t)w * (uint64_t)h <= (uint64_t)OCTVR_MAX_PREPARED_PREVIEW_PIXELS,
+            "preview larger than OCTVR_MAX_PREPARED_PREVIEW_PIXELS");
+    REQUIRE(rig, "NULL rig");
+    const int n_in = (int)rig->inputs.size(), n_ov = (int)rig->overlays.size();
+    REQUIRE(rig->out_w == m->W && rig->out_h == m->H && n_in == m->n && n_in + n_ov == m->nc,
+            "the rig is not the one the mapper was created from (output size, inputs or overlays differ)");
+    auto camera = [&](int i) -> const RigInput& { return i < n_in ? rig->inputs[i] : rig->overlays[i - n_in]; };
+    for (int i = 0; i < m->nc; i++) {
+        const RigInput& in = camera(i);
+        REQUIRE(std::equal(in.roi, in.roi + 4, m->rois.begin() + 4 * i),
+                "the rig is not the one the mapper was created from (an ROI differs)");
+        const size_t k = (size_t)in.roi[2] * in.roi[3];
+        REQUIRE(in.map1.size() == k && in.map2.size() == k && in.mask.size() == k, "rig maps do not match their ROI");
+    }
+    // the composite's own winner LUT again (the mapper dropped its per-camera maps), cut down to the result
+    // pixels the resize reads: every tap of the list is a tap of the composite's entry for that pixel, so
+    // the footprint stays as it is (tests/cpp/preview_list_check.cpp)
+    const std::vector<CompositeEntry> lut8 = winner_lut(*m, camera, 0, m->nc);
+    const PreviewListBuild<CompositeEntry> b = build_preview_list(lut8, m->W, m->H, w, h, kPvBlockEntries);
+    REQUIRE(b.pixels == (size_t)w * h && !b.entries.empty(), "preview size not representable");
+    m->pv.view = PreviewList{};
+    m->pv.entries.upload(b.entries.data(), b.entries.size());
+    m->pv.view = PreviewList{m->pv.entries.p, (uint32_t)b.entries.size(), (uint32_t)b.pixels, w, h, b.fx, b.fy};
 }
 
 void mapper_set_timing(octvr_mapper* m, int enable) {

@@ -46,6 +46,11 @@ struct octvr_mapper {
     // copies the overlays onto the result frame after the blend.  A blend-0 mapper has none: its overlays
     // are cameras of the composite LUT.
     octvr::OverlayListDev ov;
+    // The prepared preview (octvr_mapper_prepare_preview): preview_gather_kernel's tap list for one preview
+    // size, blend 0 and unscaled output only.  A stitch whose preview has that size gathers it from the source
+    // frames after the composite, on the frame slot's gains, and needs no result frame.
+    octvr::PreviewListDev pv;
+    std::vector<int> rois;  // x, y, w, h per camera: what prepare_preview checks its rig against
     // Per-frame device state that consecutive stitches would otherwise share: the gains, the feed's
     // pair totals and tickets, the composite's work queue.  A mapper is created with one slot;
     // octvr_mapper_set_frames_in_flight adds slots so that stitches issued on different streams overlap
@@ -99,6 +104,10 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
                    const PreviewOut* preview = nullptr);
 void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, const size_t* in_pitch,
                          uint8_t* const* out_dev, size_t out_pitch, const double* gains, hipStream_t s);
+// octvr_mapper_prepare_preview: the tap list of a w x h preview from `rig` (the rig the mapper was created
+// from: its size, counts and ROIs are checked, its maps are the caller's contract); 0, 0 drops the list.
+// Synchronizes the mapper.  OCTVR_E_UNSUPPORTED for a blended or scaled mapper.
+void mapper_prepare_preview(octvr_mapper* m, const octvr_rig* rig, int w, int h);
 // Waits for the last stitch of every frame slot.
 void mapper_sync(octvr_mapper& m);
 // k frame slots; the last frame's gains survive into slot 0 (octvr_mapper_set_frames_in_flight)

@@ -356,6 +356,10 @@ int octvr_mapper_stitch_preview(octvr_mapper* m, const uint8_t* const* in_dev, c
     });
 }
 
+int octvr_mapper_prepare_preview(octvr_mapper* m, const octvr_rig* rig, int preview_w, int preview_h) {
+    return guarded([&] { mapper_prepare_preview(m, rig, preview_w, preview_h); });
+}
+
 int octvr_mapper_gains(octvr_mapper* m, double* g, int n) {
     return guarded([&] {
         REQUIRE(m && g && n >= m->n, "bad arguments");
@@ -497,6 +501,8 @@ int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
                  m->mb ? 0.0 : m->tiles.staged_bytes, m->mb ? 0.0 : m->tiles.source_bytes, m->use_gain, m->n_samples, m->n_entries, m->n_chunks, m->SW, m->SH,
                  m->foot.bytes(), m->nc - m->n, m->ov.view.n_groups, m->ov.covered);
         std::string js = tmp;
+        js += ", \"preview_prepared\": [" + std::to_string(m->pv.view.dw) + ", " + std::to_string(m->pv.view.dh) +
+              "], \"preview_entries\": " + std::to_string(m->pv.view.n_entries);
         if (m->mb) js += ", " + multiband_info(*m->mb);
         else if (!m->tiles.stats.empty()) js += ", " + m->tiles.stats + ", \"items_packed\": " + std::to_string(m->tiles.n_packed);
         js += "}";

@@ -77,6 +77,8 @@ _lib.octvr_mapper_stitch_yuv420p.argtypes = [_VP, C.POINTER(_VP), C.POINTER(C.c_
                                              C.POINTER(C.c_double), C.c_int, _VP]
 _lib.octvr_mapper_stitch_preview.argtypes = [_VP, C.POINTER(_VP), C.POINTER(C.c_size_t), _VP, C.c_size_t, _VP, C.c_int,
                                              C.c_int, C.c_size_t, C.POINTER(C.c_double), C.c_int, _VP]
+if hasattr(_lib, "octvr_mapper_prepare_preview"):  # (absent from older libraries OCTVR_HIP_LIB may select for an A/B)
+    _lib.octvr_mapper_prepare_preview.argtypes = [_VP, _VP, C.c_int, C.c_int]
 _lib.octvr_mapper_gains.argtypes = [_VP, C.POINTER(C.c_double), C.c_int]
 _lib.octvr_mapper_set_frames_in_flight.argtypes = [_VP, C.c_int]
 if hasattr(_lib, "octvr_mapper_set_pixel_formats"):  # (absent from libraries built before NV12: scripts/ab.sh variants)
@@ -538,6 +540,7 @@ class Mapper:
             _check(_lib.octvr_mapper_create(mt._h, device, n, w, h, blend, int(enable_gain), scale_output[0],
                                             scale_output[1], C.byref(hd)))
         self._h = hd
+        self._mt = mt  # prepare_preview builds its list from the template's maps
         self.n = n  # frames per stitch: inputs, then overlays
         self.n_gains = n - mt.num_overlays
         self.device = device
@@ -552,7 +555,8 @@ class Mapper:
     def stitch(self, inputs, output, gains=None, stream=None, preview=None):
         """inputs: list of uint8 cuda tensors (1.5H x W "Y over [U|V]") or their FrameRefs; output likewise.
         preview: an optional (h, w, 3) uint8 cuda tensor receiving Mapper::stitch's preview_output (the RGB
-        result resized, mapper.cpp:308-312).  stream: a torch stream or a raw ctypes stream handle."""
+        result resized, mapper.cpp:308-312; of the size prepare_preview prepared: gathered from the source
+        frames, no result frame).  stream: a torch stream or a raw ctypes stream handle."""
         if isinstance(inputs, FrameRefs):
             n, ptrs, pitches = inputs.n, inputs.ptrs, inputs.pitches
         else:
@@ -575,6 +579,14 @@ class Mapper:
                                                     output.stride(0), C.c_void_p(preview.data_ptr()),
                                                     preview.shape[1], preview.shape[0], preview.stride(0), g, ng,
                                                     _stream_ptr(stream)))
+
+    def prepare_preview(self, w, h):
+        """Prepares a w x h preview that needs no result frame (octvr_mapper_prepare_preview): afterwards
+        stitch(preview=...) with a tensor of that size runs the stitch without a preview plus one gather kernel,
+        with any number of frames in flight, and gives the same bytes; other sizes stay on the result-frame
+        path.  Blend 0 and unscaled output only (OctvrError E_UNSUPPORTED otherwise); a second call replaces
+        the size, (0, 0) drops it.  Synchronizes."""
+        _check(_lib.octvr_mapper_prepare_preview(self._h, self._mt._h, int(w), int(h)))
 
     @staticmethod
     def batch_refs(frame_sets, outputs):
