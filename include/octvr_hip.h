@@ -510,6 +510,13 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
  * which thread `failing` raises an error (test hook, no GPU): the error reaches the caller as a status
  * (OCTVR_E_INVALID + octvr_last_error) instead of terminating the process; failing < 0 = none fails. */
 int octvr_debug_worker_failure(int n_threads, int failing);
+/* The gain feed's device solver (cv::solve on the GPU) on caller-given systems: `count` host systems of the
+ * same n (1..16), A row-major with row stride n (count * n * n doubles), b count * n doubles, one 256-thread
+ * workgroup per system running the function the feed kernels end in.  lean = 0: the full feed's choice (closed
+ * forms for n <= 3, the register LU for 4..8, the workgroup LU for 9..16); lean = 1: the lean feed's (closed
+ * forms for n <= 3, the workgroup LU for 4..16).  ok[k] = 1 and x[k * n ..] = the solution where system k
+ * solves, else ok[k] = 0 (x zeroed; the feed's "gains = 1 on failure" rule is the feed's own). */
+int octvr_debug_gain_solve(const double* A, const double* b, int n, int count, int lean, double* x, int* ok);
 /* Saturating float -> u8 conversion as the kernels implement it (method 0: rint + clamp in VALU,
  * method 1: v_cvt_pk_u8_f32), for a known-answer test of round-half-even and clamping on device. */
 int octvr_selftest_sat_u8(const float* in_dev, uint8_t* out_dev, int n, int method, void* stream);

@@ -287,7 +287,25 @@ int octvr_debug_project_f64(const char* json, int out_w, int out_h, int input, i
     });
 }
 
-int octvr_selftest_sat_u8(const float* in, uint8_t* out, int n, int method, void* stream) {
+int octvr_debug_gain_solve(const double* A, const double* b, int n, int count, int lean, double* x, int* ok) {
+    return guarded([&] {
+        REQUIRE(A && b && x && ok, "NULL argument");
+        REQUIRE(n >= 1 && n <= kGainMaxCams && count >= 1 && (lean == 0 || lean == 1), "bad arguments");
+        const size_t nb = (size_t)count * n, nA = nb * n;
+        DevBuf<double> Ad, bd, xd;
+        DevBuf<int> okd;
+        Ad.upload(A, nA);
+        bd.upload(b, nb);
+        xd.alloc(nb);
+        okd.alloc((size_t)count);
+        HIP_CHECK(launch_gain_solve(Ad.p, bd.p, n, count, lean != 0, xd.p, okd.p, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(x, xd.p, nb * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(ok, okd.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    });
+}
+
+int octvr_selftest_sat_u8(const float* in,uint8_t* out, int n, int method, void* stream) {
     return guarded([&] {
         REQUIRE(in && out && n >= 0 && (method == 0 || method == 1), "bad arguments");
         HIP_CHECK(launch_selftest_sat(in, out, n, method, (hipStream_t)stream));

@@ -188,6 +188,27 @@ __device__ bool solve_small(double* A, double* b, int n, double* x) {
     }
 }
 
+// cv::solve (lapack.cpp:1050-1275) on A, b in LDS, x to LDS, with the whole workgroup: the feed's choice of
+// solver.  Full feed (LEAN = false): one lane with the matrix in registers for n <= 8 (closed forms n <= 3),
+// the LU across the workgroup for 9..16.  Lean feed: the closed forms for n <= 3, the workgroup LU above (the
+// register LU would set the lean kernel's VGPR budget).  flag: one LDS int for the single lane's verdict.
+// Call with A and b visible to every thread (a barrier after they were written); returns the same flag
+// everywhere, x is written and visible where it is true.
+template <bool LEAN>
+__device__ __forceinline__ bool gain_solve(double* A, double* b, int n, double* x, int* flag) {
+    bool ok;
+    if (LEAN && n > 3) {
+        ok = lu_solve_block(A, b, n, x);
+    } else if (LEAN || n < kLuBlockMin || n <= 3) {
+        if (threadIdx.x == 0) *flag = (LEAN ? solve_small(A, b, n, x) : solve_dispatch(A, b, n, x)) ? 1 : 0;
+        __syncthreads();
+        ok = *flag != 0;
+    } else {
+        ok = lu_solve_block(A, b, n, x);
+    }
+    return ok;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Gain feed (GainCompensatorGPU::feed, exposure_compensate.cpp:223-297) — one launch.
 // Sample s of camera i (a working-scale pixel, nearest resize of the warped ROI, mapper.cpp:234-237)
@@ -534,19 +555,46 @@ __device__ __forceinline__ void gain_feed_body(const CompositeEntry* samples, co
     __syncthreads();
     if (tid < n) gain_system_row(s_I, s_N, n, tid, s_A, s_b);
     __syncthreads();
-    // cv::solve (lapack.cpp:1050-1275): one lane with the matrix in registers for n <= 8 (closed forms
-    // n <= 3); the LU across the workgroup for 9..16
-    bool ok;
-    if (LEAN && n > 3) {  // the register LU would set the lean kernel's VGPR budget
-        ok = lu_solve_block(s_A, s_b, n, s_x);
-    } else if (LEAN || n < kLuBlockMin || n <= 3) {
-        if (tid == 0) s_last = (LEAN ? solve_small(s_A, s_b, n, s_x) : solve_dispatch(s_A, s_b, n, s_x)) ? 1 : 0;
-        __syncthreads();
-        ok = s_last != 0;
-    } else {
-        ok = lu_solve_block(s_A, s_b, n, s_x);
-    }
+    const bool ok = gain_solve<LEAN>(s_A, s_b, n, s_x, &s_last);
     if (tid < n) gains[tid] = ok ? s_x[tid] : 1.0;  // cv::solve failure leaves gains_ unspecified; 1 as the oracle
+}
+
+// octvr_debug_gain_solve: workgroup k solves system k of `count` n x n systems (row-major, row stride n) with
+// gain_solve, the feed's own tail, on LDS copies as the feed holds them.  x[k * n ..] is written where ok[k] = 1.
+template <bool LEAN>
+__device__ __forceinline__ void gain_solve_body(const double* A, const double* b, int n, double* x, int* ok) {
+    __shared__ int s_flag;
+    __shared__ double s_A[kGainMaxCams * kGainMaxCams];
+    __shared__ double s_b[kGainMaxCams];
+    __shared__ double s_x[kGainMaxCams];
+    const int tid = threadIdx.x;
+    const size_t sys = blockIdx.x;
+    if (tid < n * n) s_A[tid] = A[sys * (size_t)(n * n) + tid];
+    if (tid < n) {
+        s_b[tid] = b[sys * (size_t)n + tid];
+        s_x[tid] = 0.0;
+    }
+    __syncthreads();
+    const bool good = gain_solve<LEAN>(s_A, s_b, n, s_x, &s_flag);
+    if (tid < n) x[sys * (size_t)n + tid] = good ? s_x[tid] : 0.0;
+    if (tid == 0) ok[sys] = good ? 1 : 0;
+}
+__global__ void __launch_bounds__(256) gain_solve_kernel(const double* A, const double* b, int n, double* x, int* ok) {
+    gain_solve_body<false>(A, b, n, x, ok);
+}
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(80)))
+gain_solve_lean_kernel(const double* A, const double* b, int n, double* x, int* ok) {
+    gain_solve_body<true>(A, b, n, x, ok);
+}
+
+hipError_t launch_gain_solve(const double* A, const double* b, int n, int count, bool lean, double* x, int* ok,
+                             hipStream_t s) {
+    if (n < 1 || n > kGainMaxCams || count < 1) return hipErrorInvalidValue;
+    if (lean)
+        hipLaunchKernelGGL(gain_solve_lean_kernel, dim3(count), dim3(256), 0, s, A, b, n, x, ok);
+    else
+        hipLaunchKernelGGL(gain_solve_kernel, dim3(count), dim3(256), 0, s, A, b, n, x, ok);
+    return hipGetLastError();
 }
 
 // NV12: the frames' chroma rows are U,V pairs (kPixInNv12)

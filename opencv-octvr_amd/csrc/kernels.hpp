@@ -265,6 +265,11 @@ hipError_t launch_gain_feed_batch(const FrameSet* frames, int nf, const Composit
 
 hipError_t launch_set_gains(const double* host_gains, int n, double* gains_dev, hipStream_t s);
 
+// octvr_debug_gain_solve: `count` n x n systems (device arrays, row-major) through the feed's own solver
+// selection (gain_feed.hip gain_solve), the full feed's or the lean feed's; one workgroup per system.
+hipError_t launch_gain_solve(const double* A, const double* b, int n, int count, bool lean, double* x, int* ok,
+                             hipStream_t s);
+
 // AsyncMultiMapper footprint upload (async.cpp): a run is `ng` consecutive 8-pixel groups from group g0 of
 // row pair r of camera `cam` (host_common.hpp SourceFootprint), packed at `off` as luma row 2r, luma row
 // 2r + 1, then its chroma row of U and of V; the frames are "Y over [U | V]" with pitch = width.

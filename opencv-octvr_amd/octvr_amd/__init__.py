@@ -160,6 +160,8 @@ if hasattr(_lib, "octvr_debug_pack_runs"):
                                            C.POINTER(C.c_size_t), C.c_int, _VP, C.c_size_t, _VP, C.POINTER(C.c_size_t)]
 if hasattr(_lib, "octvr_debug_worker_failure"):
     _lib.octvr_debug_worker_failure.argtypes = [C.c_int, C.c_int]
+if hasattr(_lib, "octvr_debug_gain_solve"):
+    _lib.octvr_debug_gain_solve.argtypes = [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP]
 _lib.octvr_remap_u8.argtypes = [_VP, C.c_int, C.c_int, C.c_size_t, C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_size_t,
                                 C.c_float, C.c_float, _VP, C.c_size_t, _VP]
 
@@ -271,6 +273,22 @@ def debug_gain_plan(mt, in_sizes, remap="remap"):
     p = _np.zeros(cnt.value, _np.uint16)
     _check(_lib.octvr_debug_gain_plan(mt._h, n, w, h, fl, e.ctypes.data, p.ctypes.data, cnt.value, C.byref(cnt)))
     return e, p
+
+
+def debug_gain_solve(A, b, lean=False):
+    """(x, ok) of `count` n x n systems (A: (count, n, n), b: (count, n), float64) through the gain feed's
+    device solver, one workgroup each (octvr_debug_gain_solve): lean=False the full feed's choice of solver,
+    True the lean feed's.  ok: bool per system; x rows are zero where it is False."""
+    import numpy as _np
+    A = _np.ascontiguousarray(A, _np.float64)
+    b = _np.ascontiguousarray(b, _np.float64)
+    count, n = b.shape
+    assert A.shape == (count, n, n)
+    x = _np.zeros((count, n), _np.float64)
+    ok = _np.zeros(count, _np.int32)
+    _check(_lib.octvr_debug_gain_solve(A.ctypes.data_as(_VP), b.ctypes.data_as(_VP), n, count, int(bool(lean)),
+                                       x.ctypes.data_as(_VP), ok.ctypes.data_as(_VP)))
+    return x, ok.astype(bool)
 
 
 def debug_json_number(text, exact=True):

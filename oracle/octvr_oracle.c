@@ -1077,8 +1077,10 @@ static void working_scale(int out_w, int out_h, double* ws) {
     *ws = s < 1.0 ? s : 1.0;
 }
 
-int orc_gain_feed(int n, const int* rois, const uint8_t* const* warped, const uint8_t* const* masks, int out_w,
-                  int out_h, double* gains) {
+/* The feed's system (exposure_compensate.cpp:223-296): N and I (n x n; pair counts and mean norms over the
+ * masked intersections at the working scale), then A (n x n, row-major) and b of the normal equations. */
+void orc_gain_system(int n, const int* rois, const uint8_t* const* warped, const uint8_t* const* masks, int out_w,
+                     int out_h, int* N, double* I, double* A, double* bb) {
     double ws;
     working_scale(out_w, out_h, &ws);
     int* wr = (int*)malloc(sizeof(int) * 4 * n);
@@ -1103,8 +1105,8 @@ int orc_gain_feed(int n, const int* rois, const uint8_t* const* warped, const ui
             norm[i][k] = sqrtf((float)s);
         }
     }
-    int* N = (int*)calloc((size_t)n * n, sizeof(int));
-    double* I = (double*)calloc((size_t)n * n, sizeof(double));
+    memset(N, 0, sizeof(int) * (size_t)n * n);
+    memset(I, 0, sizeof(double) * (size_t)n * n);
     for (int i = 0; i < n; i++) {
         int w = wr[4 * i + 2], h = wr[4 * i + 3], nz = 0;
         for (size_t k = 0; k < (size_t)w * h; k++) nz += smask[i][k] != 0;
@@ -1140,8 +1142,8 @@ int orc_gain_feed(int n, const int* rois, const uint8_t* const* warped, const ui
             I[j * n + i] = s2 / nn;
         }
     double alpha = 0.01, beta = 100;
-    double* A = (double*)calloc((size_t)n * n, sizeof(double));
-    double* bb = (double*)calloc((size_t)n, sizeof(double));
+    memset(A, 0, sizeof(double) * (size_t)n * n);
+    memset(bb, 0, sizeof(double) * (size_t)n);
     for (int i = 0; i < n; i++)
         for (int j = 0; j < n; j++) {
             bb[i] += beta * N[i * n + j];
@@ -1150,9 +1152,19 @@ int orc_gain_feed(int n, const int* rois, const uint8_t* const* warped, const ui
             A[i * n + i] += 2 * alpha * I[i * n + j] * I[i * n + j] * N[i * n + j];
             A[i * n + j] -= 2 * alpha * I[i * n + j] * I[j * n + i] * N[i * n + j];
         }
-    int ok = orc_solve(A, bb, n, gains);
     for (int i = 0; i < n; i++) { free(smask[i]); free(simg[i]); free(norm[i]); }
-    free(smask); free(simg); free(norm); free(wr); free(N); free(I); free(A); free(bb);
+    free(smask); free(simg); free(norm); free(wr);
+}
+
+int orc_gain_feed(int n, const int* rois, const uint8_t* const* warped, const uint8_t* const* masks, int out_w,
+                  int out_h, double* gains) {
+    int* N = (int*)malloc(sizeof(int) * (size_t)n * n);
+    double* I = (double*)malloc(sizeof(double) * (size_t)n * n);
+    double* A = (double*)malloc(sizeof(double) * (size_t)n * n);
+    double* bb = (double*)malloc(sizeof(double) * (size_t)n);
+    orc_gain_system(n, rois, warped, masks, out_w, out_h, N, I, A, bb);
+    int ok = orc_solve(A, bb, n, gains);
+    free(N); free(I); free(A); free(bb);
     return ok ? 0 : -1;
 }
 

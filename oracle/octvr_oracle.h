@@ -135,6 +135,10 @@ int orc_solve(const double* A, const double* b, int n, double* x);
  * 234-237).  warped[i]: ROI-sized u8x4 (pitch = roi_w*4), masks[i]: ROI-sized u8 LUT masks. */
 int orc_gain_feed(int n, const int* rois, const uint8_t* const* warped, const uint8_t* const* masks, int out_w,
                   int out_h, double* gains_out);
+/* The system orc_gain_feed solves, same arguments: N (n x n pair counts), I (n x n mean norms), A (n x n,
+ * row-major) and b (n) of exposure_compensate.cpp:279-296; orc_gain_feed = orc_gain_system + orc_solve. */
+void orc_gain_system(int n, const int* rois, const uint8_t* const* warped, const uint8_t* const* masks, int out_w,
+                     int out_h, int* N, double* I, double* A, double* b);
 
 /* One Mapper::stitch frame, blend=0 (mapper.cpp:193-312): YUV420 in -> YUV420 out, optional gain.
  * gains_in may be NULL (estimate) ; gains_out receives the gains used (may be NULL). */

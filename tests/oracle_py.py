@@ -465,6 +465,30 @@ def gain_feed(rois, warped, masks, out_w, out_h):
     return g
 
 
+def gain_system(rois, warped, masks, out_w, out_h):
+    """(N, I, A, b) of the system gain_feed solves (orc_gain_system), same arguments: the pair counts, the
+    mean norms, and the normal equations cv::solve receives."""
+    n = len(rois)
+    r = np.ascontiguousarray(np.array(rois, np.int32).reshape(-1))
+    warped = [np.ascontiguousarray(a) for a in warped]
+    masks = [np.ascontiguousarray(a) for a in masks]
+    wp = (C.c_void_p * n)(*[a.ctypes.data for a in warped])
+    mp = (C.c_void_p * n)(*[a.ctypes.data for a in masks])
+    N = np.zeros((n, n), np.int32)
+    I = np.zeros((n, n))
+    A = np.zeros((n, n))
+    b = np.zeros(n)
+    lib().orc_gain_system(n, r.ctypes.data_as(C.POINTER(C.c_int)), wp, mp, out_w, out_h, _p(N), _p(I), _p(A), _p(b))
+    return N, I, A, b
+
+
+def warp_inputs(in_yuv, in_sizes, map1s, map2s):
+    """The warped RGBA ROI images of a stitch (YUV420P -> RGBA, cv::remap), as stitch_frame builds them before
+    the gain feed: what gain_feed / gain_system take."""
+    return [remap_u8(yuv420_to_rgba(f, w, h), m1, m2, float(w), float(h))
+            for f, (w, h), m1, m2 in zip(in_yuv, in_sizes, map1s, map2s)]
+
+
 def stitch_frame(in_yuv, in_sizes, rois, map1s, map2s, masks, out_w, out_h, enable_gain=True, gains=None,
                  threads=1, row_band=None, blend=0, seams=None, vig=None, scale=None, preview=None, remap_tex=False):
     """One Mapper::stitch -> (YUV420P output, gains); preview=(w, h): also the preview_output image,
