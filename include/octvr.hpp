@@ -494,15 +494,27 @@ public:
         if ((int)inputs.size() != n_) throw cv::Exception(OCTVR_E_INVALID, "input count does not match the mapper");
         std::vector<const uint8_t*> p;
         std::vector<size_t> pitch;
+        int fi = 0, fo = 0;
+        pixel_formats(fi, fo);
+        // a 4:2:0 image is W x 3H/2, a packed UYVY one 2W x H (both CV_8UC1)
+        auto shaped = [](const cv::cuda::GpuMat& m, const cv::Size& sz, int fmt) {
+            if (m.type() != CV_8UC1) return false;
+            if (fmt == OCTVR_PIX_UYVY422) return m.cols == 2 * sz.width && m.rows == sz.height;
+            return m.cols == sz.width && m.rows / 3 * 2 == sz.height;
+        };
         for (int i = 0; i < n_; i++) {  // mapper.cpp:208-217
-            if (inputs[i].type() != CV_8UC1 || inputs[i].cols != sizes_[i].width ||
-                inputs[i].rows / 3 * 2 != sizes_[i].height)
+            if (!shaped(inputs[i], sizes_[i], fi))
                 throw cv::Exception(OCTVR_E_INVALID, "input frame is not a YUV420P image of the mapper's input size");
             p.push_back(inputs[i].data);
             pitch.push_back(inputs[i].step);
         }
-        if (output.empty()) output.create(out_.height * 3 / 2, out_.width, CV_8UC1);
-        if (output.type() != CV_8UC1 || output.cols != out_.width || output.rows / 3 * 2 != out_.height)
+        if (output.empty()) {
+            if (fo == OCTVR_PIX_UYVY422)
+                output.create(out_.height, 2 * out_.width, CV_8UC1);
+            else
+                output.create(out_.height * 3 / 2, out_.width, CV_8UC1);
+        }
+        if (!shaped(output, out_, fo))
             throw cv::Exception(OCTVR_E_INVALID, "output is not a YUV420P image of the output size");
         const double* g = gains.empty() ? nullptr : gains.data();
         if (!preview_output.empty()) {
@@ -532,7 +544,8 @@ public:
     // counterpart: the reference's frames are "Y over [U|V]" only): OCTVR_PIX_YUV420P, the default, or
     // OCTVR_PIX_NV12 (chroma rows of U,V byte pairs, what video decoders and encoders use).  Both are
     // W x 3H/2 CV_8U images, so stitch's shape checks hold for either (octvr_hip.h
-    // octvr_mapper_set_pixel_formats).
+    // octvr_mapper_set_pixel_formats).  OCTVR_PIX_UYVY422 (packed 4:2:2, capture and playout cards) is a
+    // 2W x H CV_8U image, converted to and from 4:2:0 frames of the mapper's own by one launch each.
     void set_pixel_formats(int in_format, int out_format) {
         detail::check(octvr_mapper_set_pixel_formats(m_.get(), in_format, out_format));
     }
@@ -585,7 +598,8 @@ public:
     // OCTVR_PIX_NV12, for the inputs (all alike) and the output independently (octvr_hip.h
     // octvr_async_set_pixel_formats; no frame may be pending).  With NV12 the second cv::Mat of an input or
     // output tuple is the interleaved U,V plane — CV_8UC1 of W x H/2 or CV_8UC2 of W/2 x H/2 — and the third
-    // may be empty.
+    // may be empty.  OCTVR_PIX_UYVY422 is valid as the input format only: the first cv::Mat of an input tuple
+    // is then the packed plane (CV_8UC1 of 2W x H), the other two may be empty; push_device takes packed frames.
     virtual void set_pixel_formats(int in_format, int out_format) = 0;
     // Not in the reference: the formats in use.
     virtual void pixel_formats(int& in_format, int& out_format) const = 0;

@@ -241,8 +241,24 @@ int octvr_mapper_set_frames_in_flight(octvr_mapper* mapper, int k);
  * themselves (no conversion pass, no intermediate frame): the result is the planar stitch of the same
  * pixels, bit for bit, with the chroma bytes rearranged.  Any other value: OCTVR_E_INVALID.  Synchronizes.
  * The octvr_async_* pipeline has its own setter, octvr_async_set_pixel_formats, which sets its mappers' formats
- * through this one; the FastMapper is not affected. */
-enum { OCTVR_PIX_YUV420P = 0, OCTVR_PIX_NV12 = 1 };
+ * through this one; the FastMapper is not affected.
+ *
+ *   OCTVR_PIX_UYVY422  packed 4:2:2, what uncompressed capture and playout cards move: a frame is H rows of 2 W
+ *                      bytes, U0 Y0 V0 Y1 per pixel pair (W, H even); `pitch` >= 2 W, any alignment, any base
+ *                      address.  Valid for either side, independently of the other.
+ * The stitch itself is a 4:2:0 one, and the chroma rules of the two conversions are this project's definitions
+ * (parity unpinned, as the BT.601 conversions are):
+ *   in  (4:2:2 -> 4:2:0): chroma row r of the 4:2:0 frame is, for U and V and per byte,
+ *                         (c[2r] + c[2r + 1] + 1) >> 1 of the packed rows 2r and 2r + 1; luma is copied;
+ *   out (4:2:0 -> 4:2:2): packed rows 2r and 2r + 1 both carry chroma row r; luma is copied.
+ * So out-then-in is the identity, and a UYVY stitch is the planar stitch of the converted frames, bit for bit.
+ * Unlike NV12 these are conversion passes: every frame slot owns one 4:2:0 frame per camera, which one launch
+ * fills from the packed frames inside the mapper's source footprint (only the bytes some kernel reads are
+ * converted), and one 4:2:0 output frame, which one launch packs into out_dev; bytes of a row of out_dev between
+ * 2 W and the pitch are not written.  The frames are allocated when the format is set and freed when it is
+ * unset.  OCTVR_E_INVALID from a stitch whose UYVY pitch is below 2 W, before any launch.  octvr_mapper_info
+ * reports "uyvy_runs", "uyvy_in_bytes" (packed bytes read per frame) and "uyvy_out_bytes" (written). */
+enum { OCTVR_PIX_YUV420P = 0, OCTVR_PIX_NV12 = 1, OCTVR_PIX_UYVY422 = 16 };
 int octvr_mapper_set_pixel_formats(octvr_mapper* mapper, int in_format, int out_format);
 int octvr_mapper_pixel_formats(const octvr_mapper* mapper, int* in_format, int* out_format);
 /* Algorithmic device bytes read+written by one launch of the composite (stitch) kernel: 4 B tiled
@@ -355,7 +371,14 @@ int octvr_async_info(const octvr_async* async, char* buf, size_t len);
  * outside every region, and between a plane's width and its pitch, are never written.  The preview stays RGB.
  * OCTVR_E_INVALID: any other value; frames pending; a change of the output format while output plane sets are
  * registered (their plane count and geometry depend on it).  A pipeline on which this was never called behaves
- * exactly as before.  Synchronizes. */
+ * exactly as before.  Synchronizes.
+ * OCTVR_PIX_UYVY422 (octvr_mapper_set_pixel_formats) is valid as the input format: in_planes[3*i] is camera i's
+ * packed plane (2 W bytes x H rows, pitch >= 2 W), the other two entries are ignored; octvr_async_push_device
+ * takes one packed device frame per camera (pitch >= 2 W).  The copy-in packs the footprint runs of the packed
+ * rows at 2 B per pixel, and one kernel converts them — a device frame's straight from the caller's frames,
+ * after ready_event — into NV12 device frames that all mappers read (they stay on NV12 input: one conversion
+ * per frame, not one per mapper).  As the output format it is OCTVR_E_UNSUPPORTED: the merge, the copy-out
+ * and the registered planes are per-plane tables of a 4:2:0 frame. */
 int octvr_async_set_pixel_formats(octvr_async* async, int in_format, int out_format);
 int octvr_async_pixel_formats(const octvr_async* async, int* in_format, int* out_format);
 /* push(inputs, output) (async.cpp:174-189): in_planes[3*i+0/1/2] = Y, U, V host planes of input i
@@ -503,9 +526,14 @@ int octvr_debug_json_number(const char* json, int flags, double* value);
  * `packed` (capacity cap) by the function the pipeline's copy-in stage calls, from planes / pitches laid out as
  * octvr_async_push's in_planes / in_pitches for `format` (OCTVR_PIX_*).  sizes[k] (optional) receives run k's
  * packed bytes, *bytes the total.  OCTVR_E_INVALID for a run outside its frame, a bad plane or a short buffer. */
+/* (For OCTVR_PIX_UYVY422 planes[3*cam] is the camera's packed plane and a run packs its two packed rows.) */
 int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const uint32_t* runs, int n_runs,
                           const uint8_t* const* planes, const size_t* pitches, int format, uint8_t* packed, size_t cap,
                           size_t* sizes, size_t* bytes);
+/* The footprint runs a UYVY-input mapper's unpack launch converts, as (camera, row pair, first group, groups)
+ * quadruples in `runs` (capacity cap runs; NULL: count only).  OCTVR_E_INVALID when the input format is not
+ * OCTVR_PIX_UYVY422. */
+int octvr_debug_mapper_uyvy_runs(const octvr_mapper* mapper, uint32_t* runs, size_t cap, size_t* count);
 /* The host build's worker threads (tiler, seam finder, blender weights, audits) on n_threads threads of
  * which thread `failing` raises an error (test hook, no GPU): the error reaches the caller as a status
  * (OCTVR_E_INVALID + octvr_last_error) instead of terminating the process; failing < 0 = none fails. */

@@ -28,7 +28,11 @@
 //     that layout themselves, and every stage here moves a Y plane and one U,V plane instead of three planes;
 //   * frames that already live on the device skip the host stages (octvr_async_push_device): the mappers read
 //     the caller's device frames in place and one kernel (async_merge.hip) places the region frames into the
-//     caller's merged device frame; such frames travel the same queues, so pop order is push order.
+//     caller's merged device frame; such frames travel the same queues, so pop order is push order;
+//   * the inputs may be packed UYVY 4:2:2 (OCTVR_PIX_UYVY422, what capture cards deliver): one plane per
+//     camera, the footprint runs of its packed rows copied and uploaded at 2 B per pixel, and one kernel
+//     (uyvy.hip) converts them into the slot's NV12 device frames — once for all mappers, which stay on NV12
+//     input; device frames are converted the same way from the caller's frames.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -49,6 +53,7 @@
 #include "abi_guard.hpp"
 #include "async_host.hpp"
 #include "mapper.hpp"
+#include "uyvy_host.hpp"
 
 using namespace octvr;
 
@@ -124,39 +129,6 @@ struct Slot {  // one frame's buffers: the packed footprint runs, the device fra
     std::vector<DevBuf<uint8_t>> in_dev, out_dev;
     FootFrames frames{};
 };
-
-// Runs of the union of the mappers' footprints: per camera and row pair, consecutive set groups, gaps of
-// up to kRunGap groups bridged (a few more bytes for fewer, longer copies).  A cell (row pair r, group g) is
-// the same pixels in either input layout, and with an even width a run's NV12 chroma row (yb bytes at byte
-// 8 g0) is as long as its planar U and V rows together (2 cb): offsets and sizes hold for both layouts.
-constexpr int kRunGap = 2;
-std::vector<FootRun> footprint_runs(const SourceFootprint& f, size_t& bytes) {
-    std::vector<FootRun> runs;
-    bytes = 0;
-    for (int i = 0; i < (int)f.w.size(); i++)
-        for (int r = 0; r < f.row_pairs(i); r++) {
-            int g = 0;
-            const int G = f.groups(i);
-            while (g < G) {
-                if (!f.test(i, r, g)) {
-                    g++;
-                    continue;
-                }
-                int e = g + 1, last = g;  // last set group of the run
-                while (e < G && e - last <= kRunGap + 1) {
-                    if (f.test(i, r, e)) last = e;
-                    e++;
-                }
-                const int ng = last - g + 1;
-                const int yb = std::min(8 * (g + ng), f.w[i]) - 8 * g;
-                const int cb = std::max(0, std::min(4 * (g + ng), f.w[i] / 2) - 4 * g);
-                runs.push_back(FootRun{(uint32_t)i | (uint32_t)r << 8, (uint32_t)g, (uint32_t)ng, (uint32_t)bytes});
-                bytes += (size_t)(2 * yb + 2 * cb);
-                g = last + 1;
-            }
-        }
-    return runs;
-}
 
 struct Job {
     std::vector<const uint8_t*> in_planes;
@@ -291,6 +263,11 @@ struct octvr_async {
     std::vector<FootRun> runs;  // what the mappers read of the inputs (footprint_runs)
     size_t packed_bytes = 0;
     DevBuf<FootRun> runs_dev;
+    // UYVY input: the unpack kernel's pieces over the same runs with their places in the packed buffers
+    // (uyvy_run_table), built when the format is first set
+    std::vector<UyvyRun> uy_table;
+    size_t uy_packed_bytes = 0;
+    DevBuf<UyvyRun> uy_table_dev;
     Slot slots[kSlots];
     // output plane sets the caller registered (octvr_async_register_output): page-locked, downloaded into
     struct RegOut {
@@ -351,6 +328,17 @@ struct octvr_async {
         if (j.device) return;  // the mappers read the caller's frames in place
         stage(j, [&] {
             uint8_t* const dst = slots[s].packed_host->p;
+            if (in_fmt == OCTVR_PIX_UYVY422) {
+                copy_in_pool.run(uy_table.size(), [&](size_t lo, size_t hi) {
+                    for (size_t k = lo; k < hi; k++) {
+                        const UyvyRun& r = uy_table[k];
+                        const int i = (int)(r.cam & 31u);
+                        uyvy_pack_run(dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng, j.in_planes[3 * i],
+                                      j.in_pitches[3 * i]);
+                    }
+                });
+                return;
+            }
             copy_in_pool.run(runs.size(), [&](size_t lo, size_t hi) {
                 for (size_t k = lo; k < hi; k++) {
                     const FootRun& r = runs[k];
@@ -369,7 +357,15 @@ struct octvr_async {
         stage(j, [&] {
             DeviceGuard dg(device);
             Slot& sl = slots[j.slot];
-            if (packed_bytes) {
+            if (in_fmt == OCTVR_PIX_UYVY422) {
+                if (uy_packed_bytes) {
+                    HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, uy_packed_bytes, hipMemcpyHostToDevice, up));
+                    UyvySources src;
+                    memset(&src, 0, sizeof src);
+                    src.packed = sl.packed_dev.p;
+                    HIP_CHECK(launch_uyvy_unpack(uy_table_dev.p, (int)uy_table.size(), src, sl.frames, up));
+                }
+            } else if (packed_bytes) {
                 HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, packed_bytes, hipMemcpyHostToDevice, up));
                 HIP_CHECK(launch_unpack_runs_layout(sl.packed_dev.p, runs_dev.p, (int)runs.size(), sl.frames,
                                                     in_fmt == OCTVR_PIX_NV12, up));
@@ -385,11 +381,22 @@ struct octvr_async {
             Slot& sl = slots[j.slot];
             std::vector<const uint8_t*> in(n_in);
             std::vector<size_t> pitch(n_in);
+            // packed UYVY device frames are converted into the slot's frames first, once for all mappers
+            const bool own = !j.device || in_fmt == OCTVR_PIX_UYVY422;
             for (int i = 0; i < n_in; i++) {
-                in[i] = j.device ? j.in_planes[i] : sl.in_dev[i].p;
-                pitch[i] = j.device ? j.in_pitches[i] : (size_t)in_w[i];
+                in[i] = own ? sl.in_dev[i].p : j.in_planes[i];
+                pitch[i] = own ? (size_t)in_w[i] : j.in_pitches[i];
             }
             if (j.device && j.ready) HIP_CHECK(hipStreamWaitEvent(comp, j.ready, 0));
+            if (j.device && in_fmt == OCTVR_PIX_UYVY422) {
+                UyvySources src;
+                memset(&src, 0, sizeof src);
+                for (int i = 0; i < n_in; i++) {
+                    src.f[i] = j.in_planes[i];
+                    src.pitch[i] = j.in_pitches[i];
+                }
+                HIP_CHECK(launch_uyvy_unpack(uy_table_dev.p, (int)uy_table.size(), src, sl.frames, comp));
+            }
             // a device frame's single region covering the whole output is stitched where it belongs
             const bool in_place = j.device && whole_frame_region();
             for (size_t k = 0; k < mappers.size(); k++) {
@@ -709,7 +716,8 @@ int octvr_async_push(octvr_async* a, const uint8_t* const* in_planes, const size
     j->in_pitches.assign(in_pitches, in_pitches + 3 * a->n_in);
     for (int i = 0; i < a->n_in; i++) {
         const size_t w = (size_t)a->in_w[i];
-        const bool bad = a->in_fmt == OCTVR_PIX_NV12
+        const bool bad = a->in_fmt == OCTVR_PIX_UYVY422 ? !in_planes[3 * i] || in_pitches[3 * i] < 2 * w
+                         : a->in_fmt == OCTVR_PIX_NV12
                              ? !in_planes[3 * i] || !in_planes[3 * i + 1] || in_pitches[3 * i] < w || in_pitches[3 * i + 1] < w
                              : !in_planes[3 * i] || !in_planes[3 * i + 1] || !in_planes[3 * i + 2] || in_pitches[3 * i] < w ||
                                    in_pitches[3 * i + 1] < w / 2 || in_pitches[3 * i + 2] < w / 2;
@@ -745,6 +753,11 @@ int octvr_async_push_device(octvr_async* a, const uint8_t* const* in_dev, const 
         for (int i = 0; i < a->n_in; i++) {
             REQUIRE(in_dev[i], "NULL input frame");
             // the limits mapper_stitch sets (mapper.cpp checked_source_frame), refused here before anything is queued
+            if (a->in_fmt == OCTVR_PIX_UYVY422) {  // a packed frame of in_h rows, converted by the pipeline
+                REQUIRE(in_pitch[i] >= (size_t)2 * (size_t)a->in_w[i], "UYVY input pitch smaller than two bytes per pixel");
+                REQUIRE((uint64_t)in_pitch[i] * (uint64_t)a->in_h[i] < 0x7FFFFFFFull, "input frame too large");
+                continue;
+            }
             REQUIRE(in_pitch[i] >= (size_t)a->in_w[i], "input pitch smaller than width");
             REQUIRE(in_pitch[i] < ((size_t)1 << 24) &&
                         (uint64_t)in_pitch[i] * (uint64_t)(a->in_h[i] + a->in_h[i] / 2) < 0x7FFFFFFFull,
@@ -865,21 +878,41 @@ int octvr_async_unregister_output(octvr_async* a, uint8_t* const* planes) {
 int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format) {
     return guarded([&] {
         REQUIRE(a, "NULL argument");
-        REQUIRE((in_format == OCTVR_PIX_YUV420P || in_format == OCTVR_PIX_NV12) &&
-                    (out_format == OCTVR_PIX_YUV420P || out_format == OCTVR_PIX_NV12),
-                "pixel format must be OCTVR_PIX_YUV420P or OCTVR_PIX_NV12");
+        auto known = [](int f) { return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || f == OCTVR_PIX_UYVY422; };
+        REQUIRE(known(in_format) && known(out_format),
+                "pixel format must be OCTVR_PIX_YUV420P, OCTVR_PIX_NV12 or OCTVR_PIX_UYVY422");
+        if (out_format == OCTVR_PIX_UYVY422)
+            throw OctvrError(OCTVR_E_UNSUPPORTED,
+                             "UYVY is an input format of the pipeline only: its merge, copy-out and registered output "
+                             "planes are per-plane tables (a Mapper writes UYVY: octvr_mapper_set_pixel_formats)");
         REQUIRE(a->pending == 0, "frames pending: pop them before changing the pixel formats");
         REQUIRE(out_format == a->out_fmt || a->reg_out.empty(),
                 "output planes are registered: unregister them before changing the output format");
         // the footprint runs are shared by both layouts because a run's NV12 chroma row is as long as its
         // U and V rows together, which needs even widths (they are, since creation)
         for (int w : a->in_w) REQUIRE(w % 2 == 0, "input widths must be even");
+        DeviceGuard dg0(a->device);
+        if (in_format == OCTVR_PIX_UYVY422 && a->uy_table.empty() && !a->runs.empty()) {
+            size_t bytes = 0;
+            std::vector<UyvyRun> t = uyvy_run_table(a->runs, a->in_w, bytes);
+            REQUIRE(bytes < ((size_t)1 << 32) && t.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
+            a->uy_table_dev.upload(t.data(), t.size());
+            for (auto& sl : a->slots)  // 4 bytes per pixel pair row against 3: larger packed buffers
+                if (sl.packed_host->n < bytes) {
+                    sl.packed_host.reset(new PinnedBuf());
+                    sl.packed_host->alloc(bytes);
+                    sl.packed_dev.alloc(bytes);
+                }
+            a->uy_table = std::move(t);
+            a->uy_packed_bytes = bytes;
+        }
+        // a UYVY pipeline converts once for all its mappers, which read its NV12 frames
+        const int mapper_in = in_format == OCTVR_PIX_UYVY422 ? OCTVR_PIX_NV12 : in_format;
         for (octvr_mapper* m : a->mappers) {
-            const int rc = octvr_mapper_set_pixel_formats(m, in_format, out_format);
+            const int rc = octvr_mapper_set_pixel_formats(m, mapper_in, out_format);
             if (rc != OCTVR_OK) throw OctvrError(rc, octvr_last_error());
         }
         if (in_format != a->in_fmt) {  // the other layout's chroma cells are elsewhere: back to the pattern
-            DeviceGuard dg(a->device);
             for (auto& sl : a->slots)
                 for (int i = 0; i < a->n_in; i++)
                     HIP_CHECK(hipMemset(sl.in_dev[i].p, 0x5A, (size_t)a->in_w[i] * (a->in_h[i] / 2 * 3)));

@@ -293,6 +293,21 @@ hipError_t launch_unpack_runs_layout(const uint8_t* packed, const FootRun* runs,
 // build_merge_table) into its place in the merged device frame `out`, one launch.
 struct MergeTable;
 hipError_t launch_merge_regions(uint8_t* out, const MergeTable& t, hipStream_t s);
+// Packed UYVY 4:2:2 frames (OCTVR_PIX_UYVY422, uyvy.hip; the arithmetic and the table in uyvy_host.hpp).
+// launch_uyvy_unpack: the groups of the table's pieces from packed 4:2:2 sources into the cameras' NV12 frames
+// `frames` (pitch = width).  The sources are the pipeline's packed upload buffer (`packed`, each piece at its
+// `off`) or, with packed NULL, one frame per camera at its pitch (>= 2 w).
+struct UyvyRun;
+struct UyvySources {
+    const uint8_t* packed;
+    const uint8_t* f[kMaxCams];
+    size_t pitch[kMaxCams];
+};
+hipError_t launch_uyvy_unpack(const UyvyRun* table, int n_pieces, const UyvySources& src, const FootFrames& frames,
+                              hipStream_t s);
+// launch_uyvy_pack: the whole w x h NV12 frame `src` (pitch = w) into the packed frame `out` at `pitch` (>= 2 w,
+// any alignment); bytes of a row past 2 w are not written.
+hipError_t launch_uyvy_pack(const uint8_t* src, int w, int h, uint8_t* out, size_t pitch, hipStream_t s);
 
 struct TiledLut {
     const TileHdr* meta;          // per staged item kMetaWords 16-byte words: the TileHdr, then kTileSlots TileSlots

@@ -85,6 +85,11 @@ void setup_overlays(octvr_mapper& m, const Camera& camera) {
 }
 
 void check_out_pitch(const octvr_mapper* m, size_t out_pitch) {
+    if (m->uy_out) {  // a packed frame of SH rows; the stitch writes the slot's own 4:2:0 frame
+        REQUIRE(out_pitch >= (size_t)2 * (size_t)m->SW, "UYVY output pitch smaller than two bytes per pixel");
+        REQUIRE((uint64_t)out_pitch * (uint64_t)m->SH < 0x7FFFFF80ull, "output frame larger than 2 GiB");
+        return;
+    }
     REQUIRE(out_pitch >= (size_t)m->SW, "output pitch smaller than width");
     // the stitch kernel addresses the output through a buffer resource with 32-bit offsets
     REQUIRE((uint64_t)out_pitch * (m->SH + m->SH / 2) < 0x7FFFFF80ull, "output frame larger than 2 GiB");
@@ -98,7 +103,57 @@ FrameSet frame_set(const octvr_mapper* m, const uint8_t* const* in_dev, const si
     return fs;
 }
 
+// The packed frames of a UYVY stitch, checked before anything is put on the stream.
+UyvySources uyvy_sources(const octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch) {
+    UyvySources us;
+    memset(&us, 0, sizeof us);
+    for (int i = 0; i < m->nc; i++) {
+        REQUIRE(in_dev[i], "bad input frame");
+        REQUIRE(in_pitch[i] >= (size_t)2 * (size_t)m->in_w[i], "UYVY input pitch smaller than two bytes per pixel");
+        REQUIRE((uint64_t)in_pitch[i] * (uint64_t)m->in_h[i] < 0x7FFFFFFFull, "input frame larger than 2 GiB");
+        us.f[i] = in_dev[i];
+        us.pitch[i] = in_pitch[i];
+    }
+    return us;
+}
+
+// The slot's unpack launch over the mapper's footprint, and the 4:2:0 frames every later stage reads.
+FrameSet uyvy_unpack_slot(const octvr_mapper* m, const octvr_mapper::FrameSlot& sl, const UyvySources& us, hipStream_t s) {
+    HIP_CHECK(launch_uyvy_unpack(m->uy_table.p, (int)m->uy_table.n, us, *sl.uy_in, s));
+    FrameSet fs;
+    memset(&fs, 0, sizeof fs);
+    for (int i = 0; i < m->nc; i++)
+        fs.f[i] = checked_source_frame(sl.uy_in->f[i], (size_t)m->in_w[i], m->in_w[i], m->in_h[i], m->vig[i].p);
+    return fs;
+}
+
 // ---- frame slots -------------------------------------------------------------------------------------
+// The slot's 4:2:0 frames of the packed UYVY sides, as the mapper's formats say (allocated or freed).  The
+// input frames hold the fixed pattern of the AsyncMultiMapper's slots outside the footprint: nothing reads it.
+void slot_uyvy(const octvr_mapper& m, octvr_mapper::SlotBufs& b, octvr_mapper::FrameSlot& sl) {
+    b.uy_in.clear();
+    b.uy_frames = FootFrames{};
+    b.uy_out.reset();
+    sl.uy_in = nullptr;
+    sl.uy_out = nullptr;
+    if (m.uy_in) {
+        b.uy_in.resize(m.nc);
+        for (int i = 0; i < m.nc; i++) {
+            const size_t bytes = (size_t)m.in_w[i] * (size_t)(m.in_h[i] / 2 * 3);
+            b.uy_in[i].alloc(bytes);
+            HIP_CHECK(hipMemset(b.uy_in[i].p, 0x5A, bytes));
+            b.uy_frames.f[i] = b.uy_in[i].p;
+            b.uy_frames.w[i] = m.in_w[i];
+            b.uy_frames.h[i] = m.in_h[i];
+        }
+        sl.uy_in = &b.uy_frames;
+    }
+    if (m.uy_out) {
+        b.uy_out.alloc((size_t)m.SW * (size_t)(m.SH / 2 * 3));
+        sl.uy_out = b.uy_out.p;
+    }
+}
+
 // One more slot: gains of 1, the feed's totals and tickets and the composite's work queue zeroed.  The
 // caller synchronises the device before a stream uses the slot.
 octvr_mapper::FrameSlot make_slot(octvr_mapper& m) {
@@ -120,6 +175,7 @@ octvr_mapper::FrameSlot make_slot(octvr_mapper& m) {
     sl.totals = b->totals.p;
     sl.tickets = b->tickets.p;
     sl.queue = b->queue.p;
+    slot_uyvy(m, *b, sl);
     m.slot_bufs.push_back(std::move(b));
     return sl;
 }
@@ -207,6 +263,65 @@ struct TimedPair {
 
 }  // namespace
 
+// Runs of a footprint: per camera and row pair, consecutive set groups, gaps of up to `gap` groups bridged
+// (a few more bytes for fewer, longer copies: the AsyncMultiMapper's host copies bridge kRunGap).  A cell (row
+// pair r, group g) is the same pixels in every input layout, and with an even width a run's NV12 chroma row (yb
+// bytes at byte 8 g0) is as long as its planar U and V rows together (2 cb): offsets and sizes hold for both
+// 4:2:0 layouts (a packed UYVY source has its own offsets, uyvy_run_table).
+std::vector<FootRun> footprint_runs(const SourceFootprint& f, size_t& bytes, int gap) {
+    std::vector<FootRun> runs;
+    bytes = 0;
+    for (int i = 0; i < (int)f.w.size(); i++)
+        for (int r = 0; r < f.row_pairs(i); r++) {
+            int g = 0;
+            const int G = f.groups(i);
+            while (g < G) {
+                if (!f.test(i, r, g)) {
+                    g++;
+                    continue;
+                }
+                int e = g + 1, last = g;  // last set group of the run
+                while (e < G && e - last <= gap + 1) {
+                    if (f.test(i, r, e)) last = e;
+                    e++;
+                }
+                const int ng = last - g + 1;
+                const int yb = std::min(8 * (g + ng), f.w[i]) - 8 * g;
+                const int cb = std::max(0, std::min(4 * (g + ng), f.w[i] / 2) - 4 * g);
+                runs.push_back(FootRun{(uint32_t)i | (uint32_t)r << 8, (uint32_t)g, (uint32_t)ng, (uint32_t)bytes});
+                bytes += (size_t)(2 * yb + 2 * cb);
+                g = last + 1;
+            }
+        }
+    return runs;
+}
+
+// The stitch of a UYVY side runs on NV12 frames of the frame slot: NV12 because a packed group's chroma is
+// already U,V pairs (one 8-byte chroma store per group in, one 8-byte chroma load per chunk out, no split into
+// a U and a V half), and because UYVY in and out then take the composite's compiled-in NV12 instance.
+void mapper_set_uyvy(octvr_mapper* m, bool in, bool out) {
+    if (in == m->uy_in && out == m->uy_out) return;
+    DeviceGuard dg(m->device);
+    if (in && !m->uy_table.p) {
+        // every source read of the mapper lies in its footprint (host_common.hpp SourceFootprint: the staged
+        // groups, the wide tiles', the multi-band remap's, the overlays' and the gain samples' taps, in either
+        // sampling convention; the gathered preview's taps are the composite's) — what the AsyncMultiMapper's
+        // footprint upload already relies on — so the unpack converts exactly these runs
+        size_t bytes420 = 0;
+        // no gaps bridged: a lane converts one group, a bridged group would only be more bytes
+        const std::vector<FootRun> runs = footprint_runs(m->foot, bytes420, 0);
+        m->uy_foot_runs = runs;
+        const std::vector<UyvyRun> table = uyvy_run_table(runs, m->in_w, m->uy_in_bytes);
+        REQUIRE(m->uy_in_bytes < ((size_t)1 << 32) && table.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
+        m->uy_runs = runs.size();
+        m->uy_table.upload(table.data(), table.size());
+    }
+    m->uy_in = in;
+    m->uy_out = out;
+    for (size_t k = 0; k < m->slots.size(); k++) slot_uyvy(*m, *m->slot_bufs[k], m->slots[k]);
+    HIP_CHECK(hipDeviceSynchronize());  // the memsets complete before any stream uses the frames
+}
+
 // Mapper::stitch (mapper.cpp:193-323).  gains_dev (device, n doubles): gains of another mapper of the
 // same inputs, copied stream-ordered (AsyncMultiMapper's gain_modes chaining, async.cpp:78-86).
 void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch, uint8_t* out_dev,
@@ -227,16 +342,35 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
     }
     check_out_pitch(m, out_pitch);
     DeviceGuard dg(m->device);
-    const FrameSet fs = frame_set(m, in_dev, in_pitch);
+    // packed UYVY sides: the slot's unpack launch fills its 4:2:0 input frames, which every stage below reads,
+    // and the stitch writes the slot's 4:2:0 output frame, which the pack launch converts at the end
+    UyvySources us;
+    FrameSet fs;
+    if (m->uy_in)
+        us = uyvy_sources(m, in_dev, in_pitch);
+    else
+        fs = frame_set(m, in_dev, in_pitch);
     REQUIRE(!m->use_gain || gains_dev || !gains || n_gains == m->n, "gains must have one entry per input");
     octvr_mapper::FrameSlot& sl = take_slot(m, s);
-    stitch_gains(m, sl, fs, gains, gains_dev, s);
     TimedPair ev(m);
     hipEvent_t e0 = ev.e0, e1 = ev.e1;
     const bool timed = e0 != nullptr;
+    // the events bracket the conversions too
+    const bool outer = m->scaled || m->mb || preview || m->uy_in || m->uy_out;
+    if (m->uy_in) {
+        if (timed) HIP_CHECK(hipEventRecord(e0, s));
+        fs = uyvy_unpack_slot(m, sl, us, s);
+    }
+    stitch_gains(m, sl, fs, gains, gains_dev, s);
+    uint8_t* const caller_out = out_dev;
+    const size_t caller_pitch = out_pitch;
+    if (m->uy_out) {
+        out_dev = sl.uy_out;
+        out_pitch = (size_t)m->SW;
+    }
     // overlays after a blend are copied onto the RGB(A) result too (mapper.cpp:279-287)
     const bool overlays = m->ov.view.n_groups > 0;
-    if (timed && (m->scaled || m->mb || preview)) HIP_CHECK(hipEventRecord(e0, s));  // else the composite records its own
+    if (timed && outer && !m->uy_in) HIP_CHECK(hipEventRecord(e0, s));  // else the composite records its own
     if (m->scaled || (preview && !gathered) || overlays) {
         // stitch at template size into the RGB(A) result, then resize + RGB -> YUV420P (mapper.cpp:290-306)
         // (one frame slot only: the result frame is shared); without scaling the resize is the identity
@@ -258,12 +392,13 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
         view.queue = sl.queue;
         // with a gathered preview the events above and below bracket the composite and the preview kernel
         HIP_CHECK(launch_stitch(fs, view, m->W, m->H, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s,
-                                gathered ? nullptr : e0, gathered ? nullptr : e1, m->pix));
+                                outer ? nullptr : e0, outer ? nullptr : e1, m->pix));
         if (gathered)
             HIP_CHECK(launch_preview_gather(fs, m->pv.view, sl.gains, m->use_gain, preview->dev, (int64_t)preview->pitch, s,
                                             m->pix));
     }
-    if (timed && (m->scaled || m->mb || preview)) HIP_CHECK(hipEventRecord(e1, s));
+    if (m->uy_out) HIP_CHECK(launch_uyvy_pack(sl.uy_out, m->SW, m->SH, caller_out, caller_pitch, s));
+    if (timed && outer) HIP_CHECK(hipEventRecord(e1, s));
     ev.keep();
     finish_slot(sl, s);
 }
@@ -288,15 +423,27 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
     check_out_pitch(m, out_pitch);
     DeviceGuard dg(m->device);
     FrameSet fs[kMaxBatch];  // every frame checked before any of them puts work on the stream
-    for (int f = 0; f < nb; f++) fs[f] = frame_set(m, in_dev + (size_t)f * m->nc, in_pitch + (size_t)f * m->nc);
+    UyvySources us[kMaxBatch];
+    for (int f = 0; f < nb; f++) {
+        if (m->uy_in)
+            us[f] = uyvy_sources(m, in_dev + (size_t)f * m->nc, in_pitch + (size_t)f * m->nc);
+        else
+            fs[f] = frame_set(m, in_dev + (size_t)f * m->nc, in_pitch + (size_t)f * m->nc);
+    }
     const double* g[kMaxBatch];
     octvr_mapper::FrameSlot* sl[kMaxBatch];
     const bool feed = m->use_gain && !gains && m->n_chunks > 0;  // every frame's gains estimated: one feed launch
     unsigned long long* tot[kMaxBatch];
     uint32_t* tick[kMaxBatch];
     double* gd[kMaxBatch];
+    TimedPair ev(m);
+    const bool outer = ev.e0 && (m->uy_in || m->uy_out);  // the events bracket the conversions too
+    uint8_t* out[kMaxBatch];
     for (int f = 0; f < nb; f++) {
         sl[f] = &take_slot(m, s);
+        if (f == 0 && outer) HIP_CHECK(hipEventRecord(ev.e0, s));
+        if (m->uy_in) fs[f] = uyvy_unpack_slot(m, *sl[f], us[f], s);  // each frame converted in its own slot
+        out[f] = m->uy_out ? sl[f]->uy_out : out_dev[f];
         if (!feed) stitch_gains(m, *sl[f], fs[f], gains ? gains + (size_t)f * m->n : nullptr, nullptr, s);
         g[f] = sl[f]->gains;
         tot[f] = sl[f]->totals;
@@ -306,11 +453,13 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
     if (feed)  // GainCompensatorGPU::feed of each frame (exposure_compensate.cpp:223-297), all in one launch
         HIP_CHECK(launch_gain_feed_batch(fs, nb, m->samples.p, m->partners.p, m->tex, m->n_chunks, m->N.p, m->n, tot, tick,
                                          gd, s, true, m->pix));
-    TimedPair ev(m);
     TiledLut view = m->tiles.view;
     view.queue = sl[0]->queue;  // this launch's work counters (the first frame's slot)
-    HIP_CHECK(launch_stitch_batch(fs, nb, view, m->W, m->H, g, m->use_gain, out_dev, (int64_t)out_pitch, s, ev.e0, ev.e1,
-                                  m->pix));
+    HIP_CHECK(launch_stitch_batch(fs, nb, view, m->W, m->H, g, m->use_gain, out, (int64_t)(m->uy_out ? (size_t)m->SW : out_pitch),
+                                  s, outer ? nullptr : ev.e0, outer ? nullptr : ev.e1, m->pix));
+    for (int f = 0; f < nb && m->uy_out; f++)
+        HIP_CHECK(launch_uyvy_pack(sl[f]->uy_out, m->SW, m->SH, out_dev[f], out_pitch, s));
+    if (outer) HIP_CHECK(hipEventRecord(ev.e1, s));
     ev.keep();
     for (int f = 0; f < nb; f++) finish_slot(*sl[f], s);
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "host_common.hpp"
+#include "uyvy_host.hpp"
 
 // =================================================================================================
 // Mapper (vr::Mapper)
@@ -62,11 +63,19 @@ struct octvr_mapper {
         uint32_t* tickets = nullptr;           // 8 per-XCD + 1 global last-workgroup-done counters
         uint32_t* queue = nullptr;
         hipEvent_t done = nullptr;  // recorded after the slot's last stitch (its stream may since be gone)
+        const octvr::FootFrames* uy_in = nullptr;  // UYVY input: the slot's 4:2:0 frame per camera (SlotBufs)
+        uint8_t* uy_out = nullptr;                 // UYVY output: the slot's 4:2:0 output frame
     };
     struct SlotBufs {
         DevBuf<double> gains;
         DevBuf<unsigned long long> totals;
         DevBuf<uint32_t> tickets, queue;
+        // Packed UYVY 4:2:2 sides (octvr_mapper_set_pixel_formats): one NV12 frame per camera (pitch = width)
+        // that the slot's unpack launch fills inside the footprint and every stage of the stitch reads, and
+        // one NV12 output frame (SW x 3 SH / 2) the stitch writes and the pack launch reads
+        std::vector<DevBuf<uint8_t>> uy_in;
+        octvr::FootFrames uy_frames{};
+        DevBuf<uint8_t> uy_out;
     };
     std::vector<FrameSlot> slots;
     std::vector<std::unique_ptr<SlotBufs>> slot_bufs;  // owners of the slots' buffers, slot by slot
@@ -74,6 +83,12 @@ struct octvr_mapper {
     int timing = 0;             // event-timing period in stitches (0 = off)
     uint64_t timed_calls = 0;
     int pix = 0;                // layouts of the inputs and the output (octvr_mapper_set_pixel_formats): kPixInNv12 | kPixOutNv12
+    // Packed UYVY 4:2:2 on either side (mapper_set_uyvy): the stitch itself then runs on the frame slot's NV12
+    // frames (`pix` carries NV12 for that side); uy_table: the unpack kernel's pieces over this mapper's footprint
+    bool uy_in = false, uy_out = false;
+    DevBuf<octvr::UyvyRun> uy_table;
+    size_t uy_runs = 0, uy_in_bytes = 0;
+    std::vector<octvr::FootRun> uy_foot_runs;  // the runs the table was cut from (octvr_debug_mapper_uyvy_runs)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events, free_events;  // recorded / reusable
     ~octvr_mapper() {
         for (auto& sl : slots)
@@ -108,6 +123,12 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
 // from: its size, counts and ROIs are checked, its maps are the caller's contract); 0, 0 drops the list.
 // Synchronizes the mapper.  OCTVR_E_UNSUPPORTED for a blended or scaled mapper.
 void mapper_prepare_preview(octvr_mapper* m, const octvr_rig* rig, int w, int h);
+// The packed UYVY sides (octvr_mapper_set_pixel_formats): allocates or frees every frame slot's 4:2:0 frames and
+// builds the unpack table from the mapper's footprint.  The mapper is synchronized by the caller.
+void mapper_set_uyvy(octvr_mapper* m, bool in, bool out);
+// Consecutive set groups of a footprint as runs, gaps of up to `gap` groups bridged; bytes: their 4:2:0 size.
+constexpr int kRunGap = 2;
+std::vector<FootRun> footprint_runs(const SourceFootprint& f, size_t& bytes, int gap = kRunGap);
 // Waits for the last stitch of every frame slot.
 void mapper_sync(octvr_mapper& m);
 // k frame slots; the last frame's gains survive into slot 0 (octvr_mapper_set_frames_in_flight)

@@ -381,20 +381,22 @@ int octvr_mapper_set_frames_in_flight(octvr_mapper* m, int k) {
 int octvr_mapper_set_pixel_formats(octvr_mapper* m, int in_format, int out_format) {
     return guarded([&] {
         REQUIRE(m, "NULL argument");
-        REQUIRE((in_format == OCTVR_PIX_YUV420P || in_format == OCTVR_PIX_NV12) &&
-                    (out_format == OCTVR_PIX_YUV420P || out_format == OCTVR_PIX_NV12),
-                "pixel format must be OCTVR_PIX_YUV420P or OCTVR_PIX_NV12");
+        auto known = [](int f) { return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || f == OCTVR_PIX_UYVY422; };
+        REQUIRE(known(in_format) && known(out_format),
+                "pixel format must be OCTVR_PIX_YUV420P, OCTVR_PIX_NV12 or OCTVR_PIX_UYVY422");
         DeviceGuard dg(m->device);
         mapper_sync(*m);  // stitches in flight keep the layouts they were issued with
-        m->pix = (in_format == OCTVR_PIX_NV12 ? kPixInNv12 : 0) | (out_format == OCTVR_PIX_NV12 ? kPixOutNv12 : 0);
+        // a packed UYVY side is converted to or from NV12 frames of the frame slot: the stitch sees NV12 there
+        mapper_set_uyvy(m, in_format == OCTVR_PIX_UYVY422, out_format == OCTVR_PIX_UYVY422);
+        m->pix = (in_format != OCTVR_PIX_YUV420P ? kPixInNv12 : 0) | (out_format != OCTVR_PIX_YUV420P ? kPixOutNv12 : 0);
     });
 }
 
 int octvr_mapper_pixel_formats(const octvr_mapper* m, int* in_format, int* out_format) {
     return guarded([&] {
         REQUIRE(m && in_format && out_format, "NULL argument");
-        *in_format = (m->pix & kPixInNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
-        *out_format = (m->pix & kPixOutNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
+        *in_format = m->uy_in ? OCTVR_PIX_UYVY422 : (m->pix & kPixInNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
+        *out_format = m->uy_out ? OCTVR_PIX_UYVY422 : (m->pix & kPixOutNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
     });
 }
 
@@ -503,6 +505,11 @@ int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
         std::string js = tmp;
         js += ", \"preview_prepared\": [" + std::to_string(m->pv.view.dw) + ", " + std::to_string(m->pv.view.dh) +
               "], \"preview_entries\": " + std::to_string(m->pv.view.n_entries);
+        // packed UYVY sides: the footprint runs the unpack launch converts and the packed bytes it reads per
+        // frame, the packed bytes the pack launch writes (0: that side is not UYVY)
+        js += ", \"uyvy_runs\": " + std::to_string(m->uy_in ? m->uy_runs : 0) +
+              ", \"uyvy_in_bytes\": " + std::to_string(m->uy_in ? m->uy_in_bytes : 0) +
+              ", \"uyvy_out_bytes\": " + std::to_string(m->uy_out ? (size_t)2 * m->SW * m->SH : 0);
         if (m->mb) js += ", " + multiband_info(*m->mb);
         else if (!m->tiles.stats.empty()) js += ", " + m->tiles.stats + ", \"items_packed\": " + std::to_string(m->tiles.n_packed);
         js += "}";

@@ -158,6 +158,8 @@ if hasattr(_lib, "octvr_debug_gain_plan"):
 if hasattr(_lib, "octvr_debug_pack_runs"):
     _lib.octvr_debug_pack_runs.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _VP, C.c_int, C.POINTER(_VP),
                                            C.POINTER(C.c_size_t), C.c_int, _VP, C.c_size_t, _VP, C.POINTER(C.c_size_t)]
+if hasattr(_lib, "octvr_debug_mapper_uyvy_runs"):
+    _lib.octvr_debug_mapper_uyvy_runs.argtypes = [_VP, _VP, C.c_size_t, C.POINTER(C.c_size_t)]
 if hasattr(_lib, "octvr_debug_worker_failure"):
     _lib.octvr_debug_worker_failure.argtypes = [C.c_int, C.c_int]
 if hasattr(_lib, "octvr_debug_gain_solve"):
@@ -221,8 +223,8 @@ def _plane_args(plane_sets):
     planes = []
     for tri in plane_sets:
         tri = list(tri)
-        if len(tri) not in (2, 3):
-            raise ValueError("a plane set is (Y, U, V), or (Y, UV) for an NV12 side")
+        if len(tri) not in (1, 2, 3):
+            raise ValueError("a plane set is (Y, U, V), (Y, UV) for an NV12 side or (UYVY,) for a packed 4:2:2 input")
         tri += [None] * (3 - len(tri))
         for p in tri:
             if p is not None:
@@ -243,7 +245,7 @@ def debug_pack_runs(in_sizes, runs, planes, fmt="yuv420p"):
     h = (C.c_int * n)(*[s[1] for s in in_sizes])
     r = np.ascontiguousarray(np.asarray(runs, np.uint32).reshape(-1, 4))
     ptr, pitch, keep = _plane_args(planes)
-    cap = int(sum(3 * 8 * int(x[3]) for x in r)) + 8
+    cap = int(sum(4 * 8 * int(x[3]) for x in r)) + 8
     packed = np.full(cap, 0x5A, np.uint8)
     sizes = np.zeros(len(r), np.uintp)
     total = C.c_size_t()
@@ -251,6 +253,16 @@ def debug_pack_runs(in_sizes, runs, planes, fmt="yuv420p"):
                                       packed.ctypes.data_as(_VP), cap, sizes.ctypes.data_as(_VP), C.byref(total)))
     assert (packed[total.value:] == 0x5A).all()
     return packed[:total.value].copy(), sizes.astype(np.int64)
+
+
+def debug_mapper_uyvy_runs(mapper):
+    """The footprint runs a "uyvy422"-input Mapper's unpack launch converts: an (n, 4) array of (camera, row
+    pair, first group, groups) (octvr_debug_mapper_uyvy_runs)."""
+    n = C.c_size_t()
+    _check(_lib.octvr_debug_mapper_uyvy_runs(mapper._h, None, 0, C.byref(n)))
+    runs = np.zeros((n.value, 4), np.uint32)
+    _check(_lib.octvr_debug_mapper_uyvy_runs(mapper._h, runs.ctypes.data_as(_VP), n.value, C.byref(n)))
+    return runs
 
 
 def debug_worker_failure(n_threads, failing):
@@ -490,16 +502,23 @@ class BatchRefs:
         assert all(o.stride(0) == self.out_pitch for o in outputs), "the outputs of a batch share one pitch"
 
 
-PIX_YUV420P, PIX_NV12 = 0, 1  # OCTVR_PIX_*
-PIX_NAMES = ("yuv420p", "nv12")
+PIX_YUV420P, PIX_NV12, PIX_UYVY422 = 0, 1, 16  # OCTVR_PIX_*
+PIX_NAMES = ("yuv420p", "nv12")  # the 4:2:0 layouts, by value
+_PIX_BY_NAME = {"yuv420p": PIX_YUV420P, "nv12": PIX_NV12, "uyvy422": PIX_UYVY422}
+_PIX_BY_VALUE = {v: k for k, v in _PIX_BY_NAME.items()}
 
 
 def _pix_value(fmt):
     if isinstance(fmt, str):
-        if fmt.lower() not in PIX_NAMES:
-            raise ValueError("pixel format must be 'yuv420p' or 'nv12'")
-        return PIX_NAMES.index(fmt.lower())
+        if fmt.lower() not in _PIX_BY_NAME:
+            raise ValueError("pixel format must be 'yuv420p', 'nv12' or 'uyvy422'")
+        return _PIX_BY_NAME[fmt.lower()]
     return int(fmt)  # the library rejects unknown values (OCTVR_E_INVALID)
+
+
+def frame_shape(fmt, w, h):
+    """(rows, columns) of a w x h frame in `fmt`: (3h/2, w) for the 4:2:0 layouts, (h, 2w) for "uyvy422"."""
+    return (int(h), 2 * int(w)) if _pix_value(fmt) == PIX_UYVY422 else (int(h) * 3 // 2, int(w))
 
 
 def _chroma_frame(frame, w, h):
@@ -529,6 +548,36 @@ def yuv420p_from_nv12(frame, w, h):
     out = np.array(f[:, :w], dtype=np.uint8, order="C")
     out[h:, :w // 2] = f[h:, 0:w:2]
     out[h:, w // 2:] = f[h:, 1:w:2]
+    return out
+
+
+def uyvy422_from_yuv420p(frame, w, h):
+    """The packed UYVY 4:2:2 frame (h rows of 2w bytes, U0 Y0 V0 Y1 per pixel pair) of a "Y over [U|V]" frame by
+    the library's output rule: packed rows 2r and 2r + 1 both carry chroma row r, luma is copied."""
+    f, w, h = _chroma_frame(frame, w, h)
+    out = np.empty((h, 2 * w), np.uint8)
+    out[:, 1::2] = f[:h, :w]
+    out[:, 0::4] = np.repeat(f[h:, :w // 2], 2, axis=0)
+    out[:, 2::4] = np.repeat(f[h:, w // 2:w], 2, axis=0)
+    return out
+
+
+def yuv420p_from_uyvy422(frame, w, h):
+    """The "Y over [U|V]" frame of a packed UYVY 4:2:2 frame (h rows, at least 2w columns) by the library's
+    input rule: chroma row r is (c[2r] + c[2r + 1] + 1) >> 1 per byte of the packed rows 2r and 2r + 1, luma is
+    copied."""
+    f = np.asarray(frame)
+    w, h = int(w), int(h)
+    if w <= 0 or h <= 0 or (w & 1) or (h & 1):
+        raise ValueError("4:2:2 frames have even width and height")
+    if f.ndim != 2 or f.dtype != np.uint8 or f.shape[0] != h or f.shape[1] < 2 * w:
+        raise ValueError("expected a uint8 frame of h rows and at least 2w columns")
+    out = np.empty((h * 3 // 2, w), np.uint8)
+    out[:h] = f[:, 1:2 * w:2]
+    c = f[:, 0:2 * w:2].astype(np.uint16)  # U,V pairs of every packed row
+    avg = ((c[0::2] + c[1::2] + 1) >> 1).astype(np.uint8)
+    out[h:, :w // 2] = avg[:, 0::2]
+    out[h:, w // 2:] = avg[:, 1::2]
     return out
 
 
@@ -637,16 +686,17 @@ class Mapper:
 
     def set_pixel_formats(self, in_format="yuv420p", out_format="yuv420p"):
         """Layouts of the input frames (all alike) and of the output of every later stitch / stitch_batch:
-        "yuv420p" ("Y over [U|V]", the default) or "nv12" (chroma rows of U,V byte pairs), or the
-        OCTVR_PIX_* values (octvr_mapper_set_pixel_formats).  Synchronizes."""
+        "yuv420p" ("Y over [U|V]", the default), "nv12" (chroma rows of U,V byte pairs) or "uyvy422" (packed
+        4:2:2, h rows of 2w bytes, converted to and from 4:2:0 frames of the mapper's own by one launch each),
+        or the OCTVR_PIX_* values (octvr_mapper_set_pixel_formats).  Synchronizes."""
         _check(_lib.octvr_mapper_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
 
     @property
     def pixel_formats(self):
-        """(input layout, output layout) as "yuv420p" / "nv12"."""
+        """(input layout, output layout) as "yuv420p" / "nv12" / "uyvy422"."""
         a, b = C.c_int(), C.c_int()
         _check(_lib.octvr_mapper_pixel_formats(self._h, C.byref(a), C.byref(b)))
-        return PIX_NAMES[a.value], PIX_NAMES[b.value]
+        return _PIX_BY_VALUE[a.value], _PIX_BY_VALUE[b.value]
 
     def traffic_bytes(self):
         b = C.c_double()
@@ -806,19 +856,22 @@ class AsyncMultiMapper:
         frame; a side that is NV12 takes (Y, UV) — UV the interleaved plane of W bytes x H/2 rows — with an
         optional third entry that is ignored.  The arrays are kept alive until the matching pop()."""
         fix = lambda p: p if p is None or p.strides[1] == 1 else np.ascontiguousarray(p)
+        inputs = [(tri,) if isinstance(tri, np.ndarray) else tuple(tri) for tri in inputs]  # a packed UYVY plane
         ip, ipt, planes = _plane_args([tuple(fix(p) for p in tri) for tri in inputs])
         op, opt, _ = _plane_args([output])
         _check(_lib.octvr_async_push(self._h, ip, ipt, op, opt))
         self._inflight.append((planes, output))
 
     @staticmethod
-    def _device_frame(t, w, h, what):
-        """t as a device frame of a w x h picture: a 2-D cuda uint8 tensor of 3h/2 rows and w columns with unit
-        column stride (a view of a larger tensor is fine: its row stride is the pitch)."""
+    def _device_frame(t, w, h, what, fmt="yuv420p"):
+        """t as a device frame of a w x h picture: a 2-D cuda uint8 tensor of 3h/2 rows and w columns (h rows and
+        2w columns for "uyvy422") with unit column stride (a view of a larger tensor is fine: its row stride is
+        the pitch)."""
+        shape = frame_shape(fmt, w, h)
         if not (hasattr(t, "is_cuda") and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and
-                tuple(t.shape) == (h * 3 // 2, w) and t.stride(1) == 1):
+                tuple(t.shape) == shape and t.stride(1) == 1):
             raise ValueError("%s: expected a cuda uint8 tensor of shape (%d, %d) with unit column stride"
-                             % (what, h * 3 // 2, w))
+                             % ((what,) + shape))
         return t
 
     def push_device(self, inputs, output, ready=None):
@@ -833,7 +886,8 @@ class AsyncMultiMapper:
         if len(inputs) != self.n:
             raise ValueError("push_device takes %d frames (every input, then every overlay), got %d"
                              % (self.n, len(inputs)))
-        ins = [self._device_frame(t, w, h, "input %d" % i) for i, (t, (w, h)) in enumerate(zip(inputs, self.in_sizes))]
+        fmt = self.pixel_formats[0]
+        ins = [self._device_frame(t, w, h, "input %d" % i, fmt) for i, (t, (w, h)) in enumerate(zip(inputs, self.in_sizes))]
         out = self._device_frame(output, self.out_size[0], self.out_size[1], "output")
         ptrs = (_VP * self.n)(*[t.data_ptr() for t in ins])
         pitches = (C.c_size_t * self.n)(*[t.stride(0) for t in ins])
@@ -876,14 +930,16 @@ class AsyncMultiMapper:
     def set_pixel_formats(self, in_format="yuv420p", out_format="yuv420p"):
         """Layouts of the host planes of every later push, "yuv420p" (the default) or "nv12", or the
         OCTVR_PIX_* values (octvr_async_set_pixel_formats): no frame may be pending, and the output format
-        cannot change while output plane sets are registered."""
+        cannot change while output plane sets are registered.  The input format may also be "uyvy422": push then
+        takes one packed plane (h rows of 2w bytes) per camera, as a one-tuple or the array itself, and
+        push_device one packed cuda tensor per camera; as the output format it is E_UNSUPPORTED."""
         _check(_lib.octvr_async_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
 
     @property
     def pixel_formats(self):
         a, b = C.c_int(), C.c_int()
         _check(_lib.octvr_async_pixel_formats(self._h, C.byref(a), C.byref(b)))
-        return PIX_NAMES[a.value], PIX_NAMES[b.value]
+        return _PIX_BY_VALUE[a.value], _PIX_BY_VALUE[b.value]
 
     def preview(self):
         """(rgb, header): the latest published preview as an (h, w, 3) uint8 array and its PreviewDataHeader
