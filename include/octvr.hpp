@@ -496,10 +496,11 @@ public:
         std::vector<size_t> pitch;
         int fi = 0, fo = 0;
         pixel_formats(fi, fo);
-        // a 4:2:0 image is W x 3H/2, a packed UYVY one 2W x H (both CV_8UC1)
+        // a 4:2:0 image is W x 3H/2, a packed UYVY or YUYV one 2W x H, a YUV422P or NV16 one W x 2H (all CV_8UC1)
         auto shaped = [](const cv::cuda::GpuMat& m, const cv::Size& sz, int fmt) {
             if (m.type() != CV_8UC1) return false;
-            if (fmt == OCTVR_PIX_UYVY422) return m.cols == 2 * sz.width && m.rows == sz.height;
+            if (fmt == OCTVR_PIX_UYVY422 || fmt == OCTVR_PIX_YUYV422) return m.cols == 2 * sz.width && m.rows == sz.height;
+            if (fmt == OCTVR_PIX_YUV422P || fmt == OCTVR_PIX_NV16) return m.cols == sz.width && m.rows == 2 * sz.height;
             return m.cols == sz.width && m.rows / 3 * 2 == sz.height;
         };
         for (int i = 0; i < n_; i++) {  // mapper.cpp:208-217
@@ -509,8 +510,10 @@ public:
             pitch.push_back(inputs[i].step);
         }
         if (output.empty()) {
-            if (fo == OCTVR_PIX_UYVY422)
+            if (fo == OCTVR_PIX_UYVY422 || fo == OCTVR_PIX_YUYV422)
                 output.create(out_.height, 2 * out_.width, CV_8UC1);
+            else if (fo == OCTVR_PIX_YUV422P || fo == OCTVR_PIX_NV16)
+                output.create(2 * out_.height, out_.width, CV_8UC1);
             else
                 output.create(out_.height * 3 / 2, out_.width, CV_8UC1);
         }
@@ -545,7 +548,8 @@ public:
     // OCTVR_PIX_NV12 (chroma rows of U,V byte pairs, what video decoders and encoders use).  Both are
     // W x 3H/2 CV_8U images, so stitch's shape checks hold for either (octvr_hip.h
     // octvr_mapper_set_pixel_formats).  OCTVR_PIX_UYVY422 (packed 4:2:2, capture and playout cards) is a
-    // 2W x H CV_8U image, converted to and from 4:2:0 frames of the mapper's own by one launch each.
+    // 2W x H CV_8U image, converted to and from 4:2:0 frames of the mapper's own by one launch each; so are
+    // OCTVR_PIX_YUYV422 (2W x H), OCTVR_PIX_YUV422P and OCTVR_PIX_NV16 (W x 2H: Y over H chroma rows).
     void set_pixel_formats(int in_format, int out_format) {
         detail::check(octvr_mapper_set_pixel_formats(m_.get(), in_format, out_format));
     }
@@ -600,6 +604,8 @@ public:
     // output tuple is the interleaved U,V plane — CV_8UC1 of W x H/2 or CV_8UC2 of W/2 x H/2 — and the third
     // may be empty.  OCTVR_PIX_UYVY422 is valid as the input format only: the first cv::Mat of an input tuple
     // is then the packed plane (CV_8UC1 of 2W x H), the other two may be empty; push_device takes packed frames.
+    // OCTVR_PIX_YUYV422 likewise; OCTVR_PIX_YUV422P takes Y (W x H), U and V (W/2 x H each), OCTVR_PIX_NV16 Y and
+    // the U,V plane (CV_8UC1 of W x H or CV_8UC2 of W/2 x H); push_device takes whole frames of the layout.
     virtual void set_pixel_formats(int in_format, int out_format) = 0;
     // Not in the reference: the formats in use.
     virtual void pixel_formats(int& in_format, int& out_format) const = 0;

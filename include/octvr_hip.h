@@ -257,8 +257,32 @@ int octvr_mapper_set_frames_in_flight(octvr_mapper* mapper, int k);
  * converted), and one 4:2:0 output frame, which one launch packs into out_dev; bytes of a row of out_dev between
  * 2 W and the pitch are not written.  The frames are allocated when the format is set and freed when it is
  * unset.  OCTVR_E_INVALID from a stitch whose UYVY pitch is below 2 W, before any launch.  octvr_mapper_info
- * reports "uyvy_runs", "uyvy_in_bytes" (packed bytes read per frame) and "uyvy_out_bytes" (written). */
-enum { OCTVR_PIX_YUV420P = 0, OCTVR_PIX_NV12 = 1, OCTVR_PIX_UYVY422 = 16 };
+ * reports "uyvy_runs", "uyvy_in_bytes" (packed bytes read per frame) and "uyvy_out_bytes" (written).
+ *
+ * The other 8-bit 4:2:2 capture layouts, each valid for either side independently of the other side's format,
+ * with the same two chroma rules, the same per-slot frames and footprint conversion (W, H even; any pitch
+ * alignment and any base address):
+ *   OCTVR_PIX_YUYV422  packed, H rows of 2 W bytes, Y0 U0 Y1 V0 per pixel pair (YUY2: V4L2 / UVC devices, HDMI
+ *                      grabbers, DirectShow); `pitch` >= 2 W
+ *   OCTVR_PIX_YUV422P  planar (ffmpeg yuv422p), W x 2H bytes: rows [0, H) are Y; row H + j holds chroma row j, U in
+ *                      bytes [0, W/2) and V in bytes [W/2, W) ("Y over [U|V]" with H chroma rows); `pitch` >= W
+ *   OCTVR_PIX_NV16     semi-planar (hardware 4:2:2 decoders, capture SDKs), W x 2H bytes: rows [0, H) are Y; row
+ *                      H + j holds chroma row j as W/2 byte pairs U,V; `pitch` >= W
+ *   in  (4:2:2 -> 4:2:0): chroma row r = (c[2r] + c[2r + 1] + 1) >> 1 per byte, for U and V; luma is copied;
+ *   out (4:2:0 -> 4:2:2): chroma rows 2r and 2r + 1 both carry chroma row r; luma is copied; bytes between a
+ *                         row's width and its pitch are never written.
+ * Out-then-in is the identity, and a stitch in any of them is the planar stitch of the converted frames, bit for
+ * bit.  A pitch below the row's width is OCTVR_E_INVALID before any launch.  octvr_mapper_info reports
+ * "yuv422_runs", "yuv422_in_bytes" and "yuv422_out_bytes" for a side in one of these three layouts (the "uyvy_*"
+ * keys stay UYVY's alone). */
+enum {
+    OCTVR_PIX_YUV420P = 0,
+    OCTVR_PIX_NV12 = 1,
+    OCTVR_PIX_UYVY422 = 16,
+    OCTVR_PIX_YUYV422 = 17,
+    OCTVR_PIX_YUV422P = 18,
+    OCTVR_PIX_NV16 = 19
+};
 int octvr_mapper_set_pixel_formats(octvr_mapper* mapper, int in_format, int out_format);
 int octvr_mapper_pixel_formats(const octvr_mapper* mapper, int* in_format, int* out_format);
 /* Algorithmic device bytes read+written by one launch of the composite (stitch) kernel: 4 B tiled
@@ -378,7 +402,13 @@ int octvr_async_info(const octvr_async* async, char* buf, size_t len);
  * rows at 2 B per pixel, and one kernel converts them — a device frame's straight from the caller's frames,
  * after ready_event — into NV12 device frames that all mappers read (they stay on NV12 input: one conversion
  * per frame, not one per mapper).  As the output format it is OCTVR_E_UNSUPPORTED: the merge, the copy-out
- * and the registered planes are per-plane tables of a 4:2:0 frame. */
+ * and the registered planes are per-plane tables of a 4:2:0 frame.
+ * OCTVR_PIX_YUYV422, OCTVR_PIX_YUV422P and OCTVR_PIX_NV16 are valid as the input format in the same way (one
+ * conversion per frame for all mappers), and OCTVR_E_UNSUPPORTED as the output format for the same reason.  Host
+ * planes of a push: YUYV in_planes[3*i] only (2 W bytes x H rows); YUV422P Y (W x H), U and V (W/2 bytes x H rows
+ * each); NV16 Y and the U,V plane (W bytes x H rows each), the third entry is ignored.  The copy-in packs a
+ * footprint run at 4 bytes per pixel of the run: its two luma rows, then its two chroma rows in the format's
+ * layout.  octvr_async_push_device takes one device frame per camera in the Mapper's layout of the format. */
 int octvr_async_set_pixel_formats(octvr_async* async, int in_format, int out_format);
 int octvr_async_pixel_formats(const octvr_async* async, int* in_format, int* out_format);
 /* push(inputs, output) (async.cpp:174-189): in_planes[3*i+0/1/2] = Y, U, V host planes of input i
@@ -526,7 +556,9 @@ int octvr_debug_json_number(const char* json, int flags, double* value);
  * `packed` (capacity cap) by the function the pipeline's copy-in stage calls, from planes / pitches laid out as
  * octvr_async_push's in_planes / in_pitches for `format` (OCTVR_PIX_*).  sizes[k] (optional) receives run k's
  * packed bytes, *bytes the total.  OCTVR_E_INVALID for a run outside its frame, a bad plane or a short buffer. */
-/* (For OCTVR_PIX_UYVY422 planes[3*cam] is the camera's packed plane and a run packs its two packed rows.) */
+/* (For OCTVR_PIX_UYVY422 planes[3*cam] is the camera's packed plane and a run packs its two packed rows.  For
+ * OCTVR_PIX_YUYV422, _YUV422P and _NV16 the planes are octvr_async_push's for the format and a run is its two luma
+ * rows, then its two chroma rows.) */
 int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const uint32_t* runs, int n_runs,
                           const uint8_t* const* planes, const size_t* pitches, int format, uint8_t* packed, size_t cap,
                           size_t* sizes, size_t* bytes);

@@ -32,7 +32,9 @@
 //   * the inputs may be packed UYVY 4:2:2 (OCTVR_PIX_UYVY422, what capture cards deliver): one plane per
 //     camera, the footprint runs of its packed rows copied and uploaded at 2 B per pixel, and one kernel
 //     (uyvy.hip) converts them into the slot's NV12 device frames — once for all mappers, which stay on NV12
-//     input; device frames are converted the same way from the caller's frames.
+//     input; device frames are converted the same way from the caller's frames;
+//   * or any other 8-bit 4:2:2 capture layout (OCTVR_PIX_YUYV422, _YUV422P, _NV16; yuv422.hip): the same table
+//     and buffers, a run packed as its two luma rows and its two chroma rows (4 B per pixel of the run too).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -54,6 +56,7 @@
 #include "async_host.hpp"
 #include "mapper.hpp"
 #include "uyvy_host.hpp"
+#include "yuv422_host.hpp"
 
 using namespace octvr;
 
@@ -265,6 +268,15 @@ struct octvr_async {
     DevBuf<FootRun> runs_dev;
     // UYVY input: the unpack kernel's pieces over the same runs with their places in the packed buffers
     // (uyvy_run_table), built when the format is first set
+    // (shared by the YUYV / YUV422P / NV16 inputs: every 4:2:2 layout packs a piece into the same 4 B per pixel)
+    bool in_422() const { return in_fmt == OCTVR_PIX_UYVY422 || yuv422_format(in_fmt); }
+    // the unpack launch of the input format over the table, from the packed buffer or the caller's frames
+    void unpack_422(const UyvySources& src, const FootFrames& frames, hipStream_t s) {
+        if (in_fmt == OCTVR_PIX_UYVY422)
+            HIP_CHECK(launch_uyvy_unpack(uy_table_dev.p, (int)uy_table.size(), src, frames, s));
+        else
+            HIP_CHECK(launch_yuv422_unpack(in_fmt - kYuv422First, uy_table_dev.p, (int)uy_table.size(), src, frames, s));
+    }
     std::vector<UyvyRun> uy_table;
     size_t uy_packed_bytes = 0;
     DevBuf<UyvyRun> uy_table_dev;
@@ -339,6 +351,17 @@ struct octvr_async {
                 });
                 return;
             }
+            if (yuv422_format(in_fmt)) {
+                copy_in_pool.run(uy_table.size(), [&](size_t lo, size_t hi) {
+                    for (size_t k = lo; k < hi; k++) {
+                        const UyvyRun& r = uy_table[k];
+                        const int i = (int)(r.cam & 31u);
+                        yuv422_pack_run(in_fmt - kYuv422First, dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng,
+                                        &j.in_planes[3 * i], &j.in_pitches[3 * i]);
+                    }
+                });
+                return;
+            }
             copy_in_pool.run(runs.size(), [&](size_t lo, size_t hi) {
                 for (size_t k = lo; k < hi; k++) {
                     const FootRun& r = runs[k];
@@ -357,13 +380,13 @@ struct octvr_async {
         stage(j, [&] {
             DeviceGuard dg(device);
             Slot& sl = slots[j.slot];
-            if (in_fmt == OCTVR_PIX_UYVY422) {
+            if (in_422()) {
                 if (uy_packed_bytes) {
                     HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, uy_packed_bytes, hipMemcpyHostToDevice, up));
                     UyvySources src;
                     memset(&src, 0, sizeof src);
                     src.packed = sl.packed_dev.p;
-                    HIP_CHECK(launch_uyvy_unpack(uy_table_dev.p, (int)uy_table.size(), src, sl.frames, up));
+                    unpack_422(src, sl.frames, up);
                 }
             } else if (packed_bytes) {
                 HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, packed_bytes, hipMemcpyHostToDevice, up));
@@ -382,20 +405,20 @@ struct octvr_async {
             std::vector<const uint8_t*> in(n_in);
             std::vector<size_t> pitch(n_in);
             // packed UYVY device frames are converted into the slot's frames first, once for all mappers
-            const bool own = !j.device || in_fmt == OCTVR_PIX_UYVY422;
+            const bool own = !j.device || in_422();
             for (int i = 0; i < n_in; i++) {
                 in[i] = own ? sl.in_dev[i].p : j.in_planes[i];
                 pitch[i] = own ? (size_t)in_w[i] : j.in_pitches[i];
             }
             if (j.device && j.ready) HIP_CHECK(hipStreamWaitEvent(comp, j.ready, 0));
-            if (j.device && in_fmt == OCTVR_PIX_UYVY422) {
+            if (j.device && in_422()) {
                 UyvySources src;
                 memset(&src, 0, sizeof src);
                 for (int i = 0; i < n_in; i++) {
                     src.f[i] = j.in_planes[i];
                     src.pitch[i] = j.in_pitches[i];
                 }
-                HIP_CHECK(launch_uyvy_unpack(uy_table_dev.p, (int)uy_table.size(), src, sl.frames, comp));
+                unpack_422(src, sl.frames, comp);
             }
             // a device frame's single region covering the whole output is stitched where it belongs
             const bool in_place = j.device && whole_frame_region();
@@ -716,8 +739,10 @@ int octvr_async_push(octvr_async* a, const uint8_t* const* in_planes, const size
     j->in_pitches.assign(in_pitches, in_pitches + 3 * a->n_in);
     for (int i = 0; i < a->n_in; i++) {
         const size_t w = (size_t)a->in_w[i];
-        const bool bad = a->in_fmt == OCTVR_PIX_UYVY422 ? !in_planes[3 * i] || in_pitches[3 * i] < 2 * w
-                         : a->in_fmt == OCTVR_PIX_NV12
+        const int f = a->in_fmt;
+        // YUV422P's planes are the planar ones (Y, U, V; h chroma rows instead of h / 2): the last branch
+        const bool bad = f == OCTVR_PIX_UYVY422 || f == OCTVR_PIX_YUYV422 ? !in_planes[3 * i] || in_pitches[3 * i] < 2 * w
+                         : f == OCTVR_PIX_NV12 || f == OCTVR_PIX_NV16
                              ? !in_planes[3 * i] || !in_planes[3 * i + 1] || in_pitches[3 * i] < w || in_pitches[3 * i + 1] < w
                              : !in_planes[3 * i] || !in_planes[3 * i + 1] || !in_planes[3 * i + 2] || in_pitches[3 * i] < w ||
                                    in_pitches[3 * i + 1] < w / 2 || in_pitches[3 * i + 2] < w / 2;
@@ -756,6 +781,11 @@ int octvr_async_push_device(octvr_async* a, const uint8_t* const* in_dev, const 
             if (a->in_fmt == OCTVR_PIX_UYVY422) {  // a packed frame of in_h rows, converted by the pipeline
                 REQUIRE(in_pitch[i] >= (size_t)2 * (size_t)a->in_w[i], "UYVY input pitch smaller than two bytes per pixel");
                 REQUIRE((uint64_t)in_pitch[i] * (uint64_t)a->in_h[i] < 0x7FFFFFFFull, "input frame too large");
+                continue;
+            }
+            if (yuv422_format(a->in_fmt)) {  // a whole frame of the layout, converted by the pipeline
+                REQUIRE(in_pitch[i] >= frame422_row_bytes(a->in_fmt, a->in_w[i]), "4:2:2 input pitch smaller than a row of the format");
+                REQUIRE((uint64_t)in_pitch[i] * (uint64_t)frame422_rows(a->in_fmt, a->in_h[i]) < 0x7FFFFFFFull, "input frame too large");
                 continue;
             }
             REQUIRE(in_pitch[i] >= (size_t)a->in_w[i], "input pitch smaller than width");
@@ -878,9 +908,15 @@ int octvr_async_unregister_output(octvr_async* a, uint8_t* const* planes) {
 int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format) {
     return guarded([&] {
         REQUIRE(a, "NULL argument");
-        auto known = [](int f) { return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || f == OCTVR_PIX_UYVY422; };
-        REQUIRE(known(in_format) && known(out_format),
-                "pixel format must be OCTVR_PIX_YUV420P, OCTVR_PIX_NV12 or OCTVR_PIX_UYVY422");
+        auto known = [](int f) {
+            return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || f == OCTVR_PIX_UYVY422 || yuv422_format(f);
+        };
+        REQUIRE(known(in_format) && known(out_format), "pixel format must be an OCTVR_PIX_* value");
+        if (yuv422_format(out_format))
+            throw OctvrError(OCTVR_E_UNSUPPORTED,
+                             "the 4:2:2 layouts are input formats of the pipeline only: its merge, copy-out and registered "
+                             "output planes are per-plane tables of a 4:2:0 frame (a Mapper writes them: "
+                             "octvr_mapper_set_pixel_formats)");
         if (out_format == OCTVR_PIX_UYVY422)
             throw OctvrError(OCTVR_E_UNSUPPORTED,
                              "UYVY is an input format of the pipeline only: its merge, copy-out and registered output "
@@ -892,7 +928,8 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
         // U and V rows together, which needs even widths (they are, since creation)
         for (int w : a->in_w) REQUIRE(w % 2 == 0, "input widths must be even");
         DeviceGuard dg0(a->device);
-        if (in_format == OCTVR_PIX_UYVY422 && a->uy_table.empty() && !a->runs.empty()) {
+        const bool in422 = in_format == OCTVR_PIX_UYVY422 || yuv422_format(in_format);
+        if (in422 && a->uy_table.empty() && !a->runs.empty()) {
             size_t bytes = 0;
             std::vector<UyvyRun> t = uyvy_run_table(a->runs, a->in_w, bytes);
             REQUIRE(bytes < ((size_t)1 << 32) && t.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
@@ -906,8 +943,8 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
             a->uy_table = std::move(t);
             a->uy_packed_bytes = bytes;
         }
-        // a UYVY pipeline converts once for all its mappers, which read its NV12 frames
-        const int mapper_in = in_format == OCTVR_PIX_UYVY422 ? OCTVR_PIX_NV12 : in_format;
+        // a 4:2:2 pipeline converts once for all its mappers, which read its NV12 frames
+        const int mapper_in = in422 ? OCTVR_PIX_NV12 : in_format;
         for (octvr_mapper* m : a->mappers) {
             const int rc = octvr_mapper_set_pixel_formats(m, mapper_in, out_format);
             if (rc != OCTVR_OK) throw OctvrError(rc, octvr_last_error());

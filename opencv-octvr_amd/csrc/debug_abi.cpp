@@ -24,14 +24,18 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
     return guarded([&] {
         REQUIRE(in_w && in_h && runs && planes && pitches && packed && bytes, "NULL argument");
         REQUIRE(n_inputs > 0 && n_inputs <= kMaxCams && n_runs >= 0, "bad counts");
-        REQUIRE(format == OCTVR_PIX_YUV420P || format == OCTVR_PIX_NV12 || format == OCTVR_PIX_UYVY422,
-                "pixel format must be OCTVR_PIX_YUV420P, OCTVR_PIX_NV12 or OCTVR_PIX_UYVY422");
-        const bool nv12 = format == OCTVR_PIX_NV12, uyvy = format == OCTVR_PIX_UYVY422;
+        REQUIRE(format == OCTVR_PIX_YUV420P || format == OCTVR_PIX_NV12 || format == OCTVR_PIX_UYVY422 || yuv422_format(format),
+                "pixel format must be an OCTVR_PIX_* value");
+        const bool nv12 = format == OCTVR_PIX_NV12, uyvy = format == OCTVR_PIX_UYVY422, y422 = yuv422_format(format);
         for (int i = 0; i < n_inputs; i++) {
             const size_t w = (size_t)in_w[i];
             REQUIRE(in_w[i] > 0 && in_h[i] > 0 && in_w[i] % 2 == 0 && in_h[i] % 2 == 0, "input sizes must be even");
-            if (uyvy) {  // one packed plane of 2 w bytes per row
+            if (uyvy || format == OCTVR_PIX_YUYV422) {  // one packed plane of 2 w bytes per row
                 REQUIRE(planes[3 * i] && pitches[3 * i] >= 2 * w, "bad input plane");
+                continue;
+            }
+            if (format == OCTVR_PIX_NV16) {  // Y and a U,V plane of w bytes per row
+                REQUIRE(planes[3 * i] && planes[3 * i + 1] && pitches[3 * i] >= w && pitches[3 * i + 1] >= w, "bad input plane");
                 continue;
             }
             REQUIRE(planes[3 * i] && planes[3 * i + 1] && pitches[3 * i] >= w, "bad input plane");
@@ -47,10 +51,12 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
             const int w = in_w[cam], h = in_h[cam];
             REQUIRE(rp < (uint32_t)h / 2 && ng > 0 && g0 < (uint32_t)(w + 7) / 8 && ng <= (uint32_t)(w + 7) / 8 - g0,
                     "run outside its frame");
-            const size_t n = (uyvy ? 4 : 3) * (size_t)run_luma_bytes(w, (int)g0, (int)ng);
+            const size_t n = (uyvy || y422 ? 4 : 3) * (size_t)run_luma_bytes(w, (int)g0, (int)ng);
             REQUIRE(off + n <= cap, "buffer too small");
-            const size_t got = uyvy ? uyvy_pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes[3 * cam], pitches[3 * cam])
-                                    : pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam, nv12);
+            const size_t got = uyvy   ? uyvy_pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes[3 * cam], pitches[3 * cam])
+                               : y422 ? yuv422_pack_run(format - kYuv422First, packed + off, w, (int)rp, (int)g0, (int)ng,
+                                                        planes + 3 * cam, pitches + 3 * cam)
+                                      : pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam, nv12);
             REQUIRE(got == n, "pack_run size");
             if (sizes) sizes[k] = got;
             off += got;
@@ -62,7 +68,7 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
 int octvr_debug_mapper_uyvy_runs(const octvr_mapper* m, uint32_t* runs, size_t cap, size_t* count) {
     return guarded([&] {
         REQUIRE(m && count, "NULL argument");
-        REQUIRE(m->uy_in, "the mapper's input format is not OCTVR_PIX_UYVY422");
+        REQUIRE(m->uy_in && m->fmt422_in == OCTVR_PIX_UYVY422, "the mapper's input format is not OCTVR_PIX_UYVY422");
         *count = m->uy_foot_runs.size();
         if (!runs) return;
         REQUIRE(cap >= m->uy_foot_runs.size(), "buffer too small");

@@ -308,6 +308,13 @@ hipError_t launch_uyvy_unpack(const UyvyRun* table, int n_pieces, const UyvySour
 // launch_uyvy_pack: the whole w x h NV12 frame `src` (pitch = w) into the packed frame `out` at `pitch` (>= 2 w,
 // any alignment); bytes of a row past 2 w are not written.
 hipError_t launch_uyvy_pack(const uint8_t* src, int w, int h, uint8_t* out, size_t pitch, hipStream_t s);
+// The other 8-bit 4:2:2 layouts (OCTVR_PIX_YUYV422 / YUV422P / NV16, yuv422.hip; `layout` is yuv422_host.hpp's
+// Yuv422Layout): the same table, sources and NV12 frames as the UYVY launches.  A frame source is the caller's
+// whole frame in the layout (YUYV: pitch >= 2 w; the planar ones: 2 h rows, pitch >= w), the packed buffer holds
+// yuv422_pack_run's pieces.  The pack writes no byte of a row past its width.
+hipError_t launch_yuv422_unpack(int layout, const UyvyRun* table, int n_pieces, const UyvySources& src,
+                                const FootFrames& frames, hipStream_t s);
+hipError_t launch_yuv422_pack(int layout, const uint8_t* src, int w, int h, uint8_t* out, size_t pitch, hipStream_t s);
 
 struct TiledLut {
     const TileHdr* meta;          // per staged item kMetaWords 16-byte words: the TileHdr, then kTileSlots TileSlots

@@ -85,9 +85,14 @@ void setup_overlays(octvr_mapper& m, const Camera& camera) {
 }
 
 void check_out_pitch(const octvr_mapper* m, size_t out_pitch) {
-    if (m->uy_out) {  // a packed frame of SH rows; the stitch writes the slot's own 4:2:0 frame
+    if (m->uy_out && m->fmt422_out == OCTVR_PIX_UYVY422) {  // a packed frame of SH rows; the stitch writes the slot's own 4:2:0 frame
         REQUIRE(out_pitch >= (size_t)2 * (size_t)m->SW, "UYVY output pitch smaller than two bytes per pixel");
         REQUIRE((uint64_t)out_pitch * (uint64_t)m->SH < 0x7FFFFF80ull, "output frame larger than 2 GiB");
+        return;
+    }
+    if (m->uy_out) {  // YUYV: SH rows of 2 SW bytes; YUV422P and NV16: 2 SH rows of SW bytes
+        REQUIRE(out_pitch >= frame422_row_bytes(m->fmt422_out, m->SW), "4:2:2 output pitch smaller than a row of the format");
+        REQUIRE((uint64_t)out_pitch * (uint64_t)frame422_rows(m->fmt422_out, m->SH) < 0x7FFFFF80ull, "output frame larger than 2 GiB");
         return;
     }
     REQUIRE(out_pitch >= (size_t)m->SW, "output pitch smaller than width");
@@ -109,8 +114,14 @@ UyvySources uyvy_sources(const octvr_mapper* m, const uint8_t* const* in_dev, co
     memset(&us, 0, sizeof us);
     for (int i = 0; i < m->nc; i++) {
         REQUIRE(in_dev[i], "bad input frame");
-        REQUIRE(in_pitch[i] >= (size_t)2 * (size_t)m->in_w[i], "UYVY input pitch smaller than two bytes per pixel");
-        REQUIRE((uint64_t)in_pitch[i] * (uint64_t)m->in_h[i] < 0x7FFFFFFFull, "input frame larger than 2 GiB");
+        if (m->fmt422_in == OCTVR_PIX_UYVY422) {
+            REQUIRE(in_pitch[i] >= (size_t)2 * (size_t)m->in_w[i], "UYVY input pitch smaller than two bytes per pixel");
+            REQUIRE((uint64_t)in_pitch[i] * (uint64_t)m->in_h[i] < 0x7FFFFFFFull, "input frame larger than 2 GiB");
+        } else {
+            REQUIRE(in_pitch[i] >= frame422_row_bytes(m->fmt422_in, m->in_w[i]), "4:2:2 input pitch smaller than a row of the format");
+            REQUIRE((uint64_t)in_pitch[i] * (uint64_t)frame422_rows(m->fmt422_in, m->in_h[i]) < 0x7FFFFFFFull,
+                    "input frame larger than 2 GiB");
+        }
         us.f[i] = in_dev[i];
         us.pitch[i] = in_pitch[i];
     }
@@ -118,8 +129,19 @@ UyvySources uyvy_sources(const octvr_mapper* m, const uint8_t* const* in_dev, co
 }
 
 // The slot's unpack launch over the mapper's footprint, and the 4:2:0 frames every later stage reads.
+// The pack launch of a 4:2:2 output side: the slot's NV12 output frame into the caller's frame.
+void pack_422(const octvr_mapper* m, const uint8_t* src, uint8_t* out, size_t pitch, hipStream_t s) {
+    if (m->fmt422_out == OCTVR_PIX_UYVY422)
+        HIP_CHECK(launch_uyvy_pack(src, m->SW, m->SH, out, pitch, s));
+    else
+        HIP_CHECK(launch_yuv422_pack(m->fmt422_out - kYuv422First, src, m->SW, m->SH, out, pitch, s));
+}
+
 FrameSet uyvy_unpack_slot(const octvr_mapper* m, const octvr_mapper::FrameSlot& sl, const UyvySources& us, hipStream_t s) {
-    HIP_CHECK(launch_uyvy_unpack(m->uy_table.p, (int)m->uy_table.n, us, *sl.uy_in, s));
+    if (m->fmt422_in == OCTVR_PIX_UYVY422)
+        HIP_CHECK(launch_uyvy_unpack(m->uy_table.p, (int)m->uy_table.n, us, *sl.uy_in, s));
+    else
+        HIP_CHECK(launch_yuv422_unpack(m->fmt422_in - kYuv422First, m->uy_table.p, (int)m->uy_table.n, us, *sl.uy_in, s));
     FrameSet fs;
     memset(&fs, 0, sizeof fs);
     for (int i = 0; i < m->nc; i++)
@@ -299,7 +321,11 @@ std::vector<FootRun> footprint_runs(const SourceFootprint& f, size_t& bytes, int
 // The stitch of a UYVY side runs on NV12 frames of the frame slot: NV12 because a packed group's chroma is
 // already U,V pairs (one 8-byte chroma store per group in, one 8-byte chroma load per chunk out, no split into
 // a U and a V half), and because UYVY in and out then take the composite's compiled-in NV12 instance.
-void mapper_set_uyvy(octvr_mapper* m, bool in, bool out) {
+// The other 4:2:2 layouts take the same frames, table and runs; only the two launches differ (pack_422).
+void mapper_set_uyvy(octvr_mapper* m, int in_fmt, int out_fmt) {
+    const bool in = in_fmt != 0, out = out_fmt != 0;
+    m->fmt422_in = in_fmt;  // the slot frames depend on the sides being 4:2:2 only, not on the layout
+    m->fmt422_out = out_fmt;
     if (in == m->uy_in && out == m->uy_out) return;
     DeviceGuard dg(m->device);
     if (in && !m->uy_table.p) {
@@ -397,7 +423,7 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
             HIP_CHECK(launch_preview_gather(fs, m->pv.view, sl.gains, m->use_gain, preview->dev, (int64_t)preview->pitch, s,
                                             m->pix));
     }
-    if (m->uy_out) HIP_CHECK(launch_uyvy_pack(sl.uy_out, m->SW, m->SH, caller_out, caller_pitch, s));
+    if (m->uy_out) pack_422(m, sl.uy_out, caller_out, caller_pitch, s);
     if (timed && outer) HIP_CHECK(hipEventRecord(e1, s));
     ev.keep();
     finish_slot(sl, s);
@@ -457,8 +483,7 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
     view.queue = sl[0]->queue;  // this launch's work counters (the first frame's slot)
     HIP_CHECK(launch_stitch_batch(fs, nb, view, m->W, m->H, g, m->use_gain, out, (int64_t)(m->uy_out ? (size_t)m->SW : out_pitch),
                                   s, outer ? nullptr : ev.e0, outer ? nullptr : ev.e1, m->pix));
-    for (int f = 0; f < nb && m->uy_out; f++)
-        HIP_CHECK(launch_uyvy_pack(sl[f]->uy_out, m->SW, m->SH, out_dev[f], out_pitch, s));
+    for (int f = 0; f < nb && m->uy_out; f++) pack_422(m, sl[f]->uy_out, out_dev[f], out_pitch, s);
     if (outer) HIP_CHECK(hipEventRecord(ev.e1, s));
     ev.keep();
     for (int f = 0; f < nb; f++) finish_slot(*sl[f], s);

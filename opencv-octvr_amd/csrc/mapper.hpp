@@ -8,6 +8,7 @@
 
 #include "host_common.hpp"
 #include "uyvy_host.hpp"
+#include "yuv422_host.hpp"
 
 // =================================================================================================
 // Mapper (vr::Mapper)
@@ -85,7 +86,11 @@ struct octvr_mapper {
     int pix = 0;                // layouts of the inputs and the output (octvr_mapper_set_pixel_formats): kPixInNv12 | kPixOutNv12
     // Packed UYVY 4:2:2 on either side (mapper_set_uyvy): the stitch itself then runs on the frame slot's NV12
     // frames (`pix` carries NV12 for that side); uy_table: the unpack kernel's pieces over this mapper's footprint
+    // The other 4:2:2 layouts (YUYV, YUV422P, NV16; yuv422.hip) share all of it — the slot frames, the table, the
+    // footprint runs: uy_in / uy_out say that the side is 4:2:2, fmt422_in / fmt422_out which layout
+    // (OCTVR_PIX_UYVY422 .. OCTVR_PIX_NV16; 0: the side is 4:2:0)
     bool uy_in = false, uy_out = false;
+    int fmt422_in = 0, fmt422_out = 0;
     DevBuf<octvr::UyvyRun> uy_table;
     size_t uy_runs = 0, uy_in_bytes = 0;
     std::vector<octvr::FootRun> uy_foot_runs;  // the runs the table was cut from (octvr_debug_mapper_uyvy_runs)
@@ -125,7 +130,11 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
 void mapper_prepare_preview(octvr_mapper* m, const octvr_rig* rig, int w, int h);
 // The packed UYVY sides (octvr_mapper_set_pixel_formats): allocates or frees every frame slot's 4:2:0 frames and
 // builds the unpack table from the mapper's footprint.  The mapper is synchronized by the caller.
-void mapper_set_uyvy(octvr_mapper* m, bool in, bool out);
+// in / out: the side's 4:2:2 format (OCTVR_PIX_UYVY422, _YUYV422, _YUV422P, _NV16) or 0 for a 4:2:0 side.
+void mapper_set_uyvy(octvr_mapper* m, int in, int out);
+// Bytes of a row and rows of a w x h frame in a 4:2:2 format.
+inline size_t frame422_row_bytes(int fmt, int w) { return (fmt == OCTVR_PIX_UYVY422 || fmt == OCTVR_PIX_YUYV422 ? 2 : 1) * (size_t)w; }
+inline size_t frame422_rows(int fmt, int h) { return (fmt == OCTVR_PIX_UYVY422 || fmt == OCTVR_PIX_YUYV422 ? 1 : 2) * (size_t)h; }
 // Consecutive set groups of a footprint as runs, gaps of up to `gap` groups bridged; bytes: their 4:2:0 size.
 constexpr int kRunGap = 2;
 std::vector<FootRun> footprint_runs(const SourceFootprint& f, size_t& bytes, int gap = kRunGap);

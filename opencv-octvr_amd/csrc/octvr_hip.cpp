@@ -381,13 +381,18 @@ int octvr_mapper_set_frames_in_flight(octvr_mapper* m, int k) {
 int octvr_mapper_set_pixel_formats(octvr_mapper* m, int in_format, int out_format) {
     return guarded([&] {
         REQUIRE(m, "NULL argument");
-        auto known = [](int f) { return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || f == OCTVR_PIX_UYVY422; };
+        auto known = [](int f) {
+            return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || f == OCTVR_PIX_UYVY422 || yuv422_format(f);
+        };
         REQUIRE(known(in_format) && known(out_format),
-                "pixel format must be OCTVR_PIX_YUV420P, OCTVR_PIX_NV12 or OCTVR_PIX_UYVY422");
+                "pixel format must be OCTVR_PIX_YUV420P, OCTVR_PIX_NV12, OCTVR_PIX_UYVY422, OCTVR_PIX_YUYV422, "
+                "OCTVR_PIX_YUV422P or OCTVR_PIX_NV16");
         DeviceGuard dg(m->device);
         mapper_sync(*m);  // stitches in flight keep the layouts they were issued with
         // a packed UYVY side is converted to or from NV12 frames of the frame slot: the stitch sees NV12 there
-        mapper_set_uyvy(m, in_format == OCTVR_PIX_UYVY422, out_format == OCTVR_PIX_UYVY422);
+        // (so is a side in any other 4:2:2 layout)
+        auto is422 = [](int f) { return f == OCTVR_PIX_UYVY422 || yuv422_format(f); };
+        mapper_set_uyvy(m, is422(in_format) ? in_format : 0, is422(out_format) ? out_format : 0);
         m->pix = (in_format != OCTVR_PIX_YUV420P ? kPixInNv12 : 0) | (out_format != OCTVR_PIX_YUV420P ? kPixOutNv12 : 0);
     });
 }
@@ -395,8 +400,8 @@ int octvr_mapper_set_pixel_formats(octvr_mapper* m, int in_format, int out_forma
 int octvr_mapper_pixel_formats(const octvr_mapper* m, int* in_format, int* out_format) {
     return guarded([&] {
         REQUIRE(m && in_format && out_format, "NULL argument");
-        *in_format = m->uy_in ? OCTVR_PIX_UYVY422 : (m->pix & kPixInNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
-        *out_format = m->uy_out ? OCTVR_PIX_UYVY422 : (m->pix & kPixOutNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
+        *in_format = m->uy_in ? m->fmt422_in : (m->pix & kPixInNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
+        *out_format = m->uy_out ? m->fmt422_out : (m->pix & kPixOutNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
     });
 }
 
@@ -507,9 +512,15 @@ int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
               "], \"preview_entries\": " + std::to_string(m->pv.view.n_entries);
         // packed UYVY sides: the footprint runs the unpack launch converts and the packed bytes it reads per
         // frame, the packed bytes the pack launch writes (0: that side is not UYVY)
-        js += ", \"uyvy_runs\": " + std::to_string(m->uy_in ? m->uy_runs : 0) +
-              ", \"uyvy_in_bytes\": " + std::to_string(m->uy_in ? m->uy_in_bytes : 0) +
-              ", \"uyvy_out_bytes\": " + std::to_string(m->uy_out ? (size_t)2 * m->SW * m->SH : 0);
+        const bool uy_i = m->uy_in && m->fmt422_in == OCTVR_PIX_UYVY422, uy_o = m->uy_out && m->fmt422_out == OCTVR_PIX_UYVY422;
+        js += ", \"uyvy_runs\": " + std::to_string(uy_i ? m->uy_runs : 0) +
+              ", \"uyvy_in_bytes\": " + std::to_string(uy_i ? m->uy_in_bytes : 0) +
+              ", \"uyvy_out_bytes\": " + std::to_string(uy_o ? (size_t)2 * m->SW * m->SH : 0);
+        // the same three figures for a YUYV, YUV422P or NV16 side (every 4:2:2 layout is 2 bytes per pixel)
+        const bool y2_i = m->uy_in && !uy_i, y2_o = m->uy_out && !uy_o;
+        js += ", \"yuv422_runs\": " + std::to_string(y2_i ? m->uy_runs : 0) +
+              ", \"yuv422_in_bytes\": " + std::to_string(y2_i ? m->uy_in_bytes : 0) +
+              ", \"yuv422_out_bytes\": " + std::to_string(y2_o ? (size_t)2 * m->SW * m->SH : 0);
         if (m->mb) js += ", " + multiband_info(*m->mb);
         else if (!m->tiles.stats.empty()) js += ", " + m->tiles.stats + ", \"items_packed\": " + std::to_string(m->tiles.n_packed);
         js += "}";

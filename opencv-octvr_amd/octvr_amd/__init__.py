@@ -503,22 +503,30 @@ class BatchRefs:
 
 
 PIX_YUV420P, PIX_NV12, PIX_UYVY422 = 0, 1, 16  # OCTVR_PIX_*
+PIX_YUYV422, PIX_YUV422P, PIX_NV16 = 17, 18, 19  # the other 8-bit 4:2:2 capture layouts
 PIX_NAMES = ("yuv420p", "nv12")  # the 4:2:0 layouts, by value
-_PIX_BY_NAME = {"yuv420p": PIX_YUV420P, "nv12": PIX_NV12, "uyvy422": PIX_UYVY422}
+_PIX_BY_NAME = {"yuv420p": PIX_YUV420P, "nv12": PIX_NV12, "uyvy422": PIX_UYVY422, "yuyv422": PIX_YUYV422,
+                "yuv422p": PIX_YUV422P, "nv16": PIX_NV16}
 _PIX_BY_VALUE = {v: k for k, v in _PIX_BY_NAME.items()}
 
 
 def _pix_value(fmt):
     if isinstance(fmt, str):
         if fmt.lower() not in _PIX_BY_NAME:
-            raise ValueError("pixel format must be 'yuv420p', 'nv12' or 'uyvy422'")
+            raise ValueError("pixel format must be 'yuv420p', 'nv12', 'uyvy422', 'yuyv422', 'yuv422p' or 'nv16'")
         return _PIX_BY_NAME[fmt.lower()]
     return int(fmt)  # the library rejects unknown values (OCTVR_E_INVALID)
 
 
 def frame_shape(fmt, w, h):
-    """(rows, columns) of a w x h frame in `fmt`: (3h/2, w) for the 4:2:0 layouts, (h, 2w) for "uyvy422"."""
-    return (int(h), 2 * int(w)) if _pix_value(fmt) == PIX_UYVY422 else (int(h) * 3 // 2, int(w))
+    """(rows, columns) of a w x h frame in `fmt`: (3h/2, w) for the 4:2:0 layouts, (h, 2w) for "uyvy422" and
+    "yuyv422", (2h, w) for "yuv422p" and "nv16"."""
+    v = _pix_value(fmt)
+    if v in (PIX_UYVY422, PIX_YUYV422):
+        return (int(h), 2 * int(w))
+    if v in (PIX_YUV422P, PIX_NV16):
+        return (2 * int(h), int(w))
+    return (int(h) * 3 // 2, int(w))
 
 
 def _chroma_frame(frame, w, h):
@@ -578,6 +586,70 @@ def yuv420p_from_uyvy422(frame, w, h):
     avg = ((c[0::2] + c[1::2] + 1) >> 1).astype(np.uint8)
     out[h:, :w // 2] = avg[:, 0::2]
     out[h:, w // 2:] = avg[:, 1::2]
+    return out
+
+
+def yuv422_from_yuv420p(fmt, frame, w, h):
+    """The frame in the 4:2:2 layout `fmt` ("uyvy422", "yuyv422", "yuv422p", "nv16" or the PIX_* value; shape
+    frame_shape(fmt, w, h)) of a "Y over [U|V]" frame by the library's output rule: chroma rows 2r and 2r + 1 both
+    carry chroma row r, luma is copied."""
+    v = _pix_value(fmt)
+    if v == PIX_UYVY422:
+        return uyvy422_from_yuv420p(frame, w, h)
+    if v not in (PIX_YUYV422, PIX_YUV422P, PIX_NV16):
+        raise ValueError("not a 4:2:2 layout")
+    f, w, h = _chroma_frame(frame, w, h)
+    u = np.repeat(f[h:, :w // 2], 2, axis=0)
+    vv = np.repeat(f[h:, w // 2:w], 2, axis=0)
+    out = np.empty(frame_shape(v, w, h), np.uint8)
+    if v == PIX_YUYV422:
+        out[:, 0::2] = f[:h, :w]
+        out[:, 1::4] = u
+        out[:, 3::4] = vv
+        return out
+    out[:h] = f[:h, :w]
+    if v == PIX_YUV422P:
+        out[h:, :w // 2] = u
+        out[h:, w // 2:] = vv
+    else:
+        out[h:, 0::2] = u
+        out[h:, 1::2] = vv
+    return out
+
+
+def yuv422_planes(fmt, frame, w, h):
+    """(luma, U, V) of a frame in the 4:2:2 layout `fmt`, each as an array of h rows (U and V w/2 columns wide);
+    columns of `frame` past a row's width (a pitch) are dropped."""
+    v = _pix_value(fmt)
+    f = np.asarray(frame)
+    w, h = int(w), int(h)
+    if w <= 0 or h <= 0 or (w & 1) or (h & 1):
+        raise ValueError("4:2:2 frames have even width and height")
+    if v not in (PIX_UYVY422, PIX_YUYV422, PIX_YUV422P, PIX_NV16):
+        raise ValueError("not a 4:2:2 layout")
+    rows, cols = frame_shape(v, w, h)
+    if f.ndim != 2 or f.dtype != np.uint8 or f.shape[0] != rows or f.shape[1] < cols:
+        raise ValueError("expected a uint8 frame of %d rows and at least %d columns" % (rows, cols))
+    f = f[:, :cols]
+    if v == PIX_UYVY422:
+        return f[:, 1::2], f[:, 0::4], f[:, 2::4]
+    if v == PIX_YUYV422:
+        return f[:, 0::2], f[:, 1::4], f[:, 3::4]
+    if v == PIX_YUV422P:
+        return f[:h], f[h:, :w // 2], f[h:, w // 2:]
+    return f[:h], f[h:, 0::2], f[h:, 1::2]
+
+
+def yuv420p_from_yuv422(fmt, frame, w, h):
+    """The "Y over [U|V]" frame of a frame in the 4:2:2 layout `fmt` by the library's input rule: chroma row r is
+    (c[2r] + c[2r + 1] + 1) >> 1 per byte of chroma rows 2r and 2r + 1, for U and V; luma is copied."""
+    y, u, v = yuv422_planes(fmt, frame, w, h)
+    w, h = int(w), int(h)
+    out = np.empty((h * 3 // 2, w), np.uint8)
+    out[:h] = y
+    for plane, x0 in ((u, 0), (v, w // 2)):
+        c = plane.astype(np.uint16)
+        out[h:, x0:x0 + w // 2] = ((c[0::2] + c[1::2] + 1) >> 1).astype(np.uint8)
     return out
 
 
@@ -686,14 +758,16 @@ class Mapper:
 
     def set_pixel_formats(self, in_format="yuv420p", out_format="yuv420p"):
         """Layouts of the input frames (all alike) and of the output of every later stitch / stitch_batch:
-        "yuv420p" ("Y over [U|V]", the default), "nv12" (chroma rows of U,V byte pairs) or "uyvy422" (packed
+        "yuv420p" ("Y over [U|V]", the default), "nv12" (chroma rows of U,V byte pairs), "uyvy422" (packed
         4:2:2, h rows of 2w bytes, converted to and from 4:2:0 frames of the mapper's own by one launch each),
-        or the OCTVR_PIX_* values (octvr_mapper_set_pixel_formats).  Synchronizes."""
+        "yuyv422" (packed, Y0 U0 Y1 V0), "yuv422p" or "nv16" (2h rows of w bytes: Y over h chroma rows, [U|V]
+        halves or U,V pairs; frame_shape gives each layout's shape), or the OCTVR_PIX_* values
+        (octvr_mapper_set_pixel_formats).  Synchronizes."""
         _check(_lib.octvr_mapper_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
 
     @property
     def pixel_formats(self):
-        """(input layout, output layout) as "yuv420p" / "nv12" / "uyvy422"."""
+        """(input layout, output layout) as "yuv420p" / "nv12" / "uyvy422" / "yuyv422" / "yuv422p" / "nv16"."""
         a, b = C.c_int(), C.c_int()
         _check(_lib.octvr_mapper_pixel_formats(self._h, C.byref(a), C.byref(b)))
         return _PIX_BY_VALUE[a.value], _PIX_BY_VALUE[b.value]
@@ -854,7 +928,10 @@ class AsyncMultiMapper:
     def push(self, inputs, output):
         """inputs: list of (Y, U, V) uint8 numpy planes per camera; output: (Y, U, V) planes of the merged
         frame; a side that is NV12 takes (Y, UV) — UV the interleaved plane of W bytes x H/2 rows — with an
-        optional third entry that is ignored.  The arrays are kept alive until the matching pop()."""
+        optional third entry that is ignored.  4:2:2 inputs (set_pixel_formats): "uyvy422" / "yuyv422" one packed
+        plane (h rows of 2w bytes), as a one-tuple or the array itself; "yuv422p" (Y, U, V) with U and V of h rows
+        of w/2 bytes; "nv16" (Y, UV) with UV of h rows of w bytes.  The arrays are kept alive until the matching
+        pop()."""
         fix = lambda p: p if p is None or p.strides[1] == 1 else np.ascontiguousarray(p)
         inputs = [(tri,) if isinstance(tri, np.ndarray) else tuple(tri) for tri in inputs]  # a packed UYVY plane
         ip, ipt, planes = _plane_args([tuple(fix(p) for p in tri) for tri in inputs])
@@ -865,8 +942,8 @@ class AsyncMultiMapper:
     @staticmethod
     def _device_frame(t, w, h, what, fmt="yuv420p"):
         """t as a device frame of a w x h picture: a 2-D cuda uint8 tensor of 3h/2 rows and w columns (h rows and
-        2w columns for "uyvy422") with unit column stride (a view of a larger tensor is fine: its row stride is
-        the pitch)."""
+        2w columns for "uyvy422"; frame_shape(fmt, w, h) in general) with unit column stride (a view of a larger
+        tensor is fine: its row stride is the pitch)."""
         shape = frame_shape(fmt, w, h)
         if not (hasattr(t, "is_cuda") and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and
                 tuple(t.shape) == shape and t.stride(1) == 1):
@@ -932,7 +1009,9 @@ class AsyncMultiMapper:
         OCTVR_PIX_* values (octvr_async_set_pixel_formats): no frame may be pending, and the output format
         cannot change while output plane sets are registered.  The input format may also be "uyvy422": push then
         takes one packed plane (h rows of 2w bytes) per camera, as a one-tuple or the array itself, and
-        push_device one packed cuda tensor per camera; as the output format it is E_UNSUPPORTED."""
+        push_device one packed cuda tensor per camera; as the output format it is E_UNSUPPORTED.  "yuyv422",
+        "yuv422p" and "nv16" likewise: input only, planes as push() describes, push_device one cuda tensor of
+        frame_shape(fmt, w, h) per camera."""
         _check(_lib.octvr_async_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
 
     @property
