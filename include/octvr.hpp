@@ -496,8 +496,13 @@ public:
         std::vector<size_t> pitch;
         int fi = 0, fo = 0;
         pixel_formats(fi, fo);
-        // a 4:2:0 image is W x 3H/2, a packed UYVY or YUYV one 2W x H, a YUV422P or NV16 one W x 2H (all CV_8UC1)
+        // a 4:2:0 image is W x 3H/2, a packed UYVY or YUYV one 2W x H, a YUV422P or NV16 one W x 2H (all CV_8UC1); a
+        // 10-bit one is CV_MAKETYPE(CV_16U, 1) of W columns, or CV_8UC1 of 2W byte columns, with 3H/2 (P010, YUV420P10) or 2H rows
         auto shaped = [](const cv::cuda::GpuMat& m, const cv::Size& sz, int fmt) {
+            if (fmt >= OCTVR_PIX_P010 && fmt <= OCTVR_PIX_YUV422P10) {
+                const int rows = fmt >= OCTVR_PIX_P210 ? 2 * sz.height : sz.height / 2 * 3;
+                return m.rows == rows && ((m.type() == CV_MAKETYPE(CV_16U, 1) && m.cols == sz.width) || (m.type() == CV_8UC1 && m.cols == 2 * sz.width));
+            }
             if (m.type() != CV_8UC1) return false;
             if (fmt == OCTVR_PIX_UYVY422 || fmt == OCTVR_PIX_YUYV422) return m.cols == 2 * sz.width && m.rows == sz.height;
             if (fmt == OCTVR_PIX_YUV422P || fmt == OCTVR_PIX_NV16) return m.cols == sz.width && m.rows == 2 * sz.height;
@@ -510,7 +515,9 @@ public:
             pitch.push_back(inputs[i].step);
         }
         if (output.empty()) {
-            if (fo == OCTVR_PIX_UYVY422 || fo == OCTVR_PIX_YUYV422)
+            if (fo >= OCTVR_PIX_P010 && fo <= OCTVR_PIX_YUV422P10)
+                output.create(fo >= OCTVR_PIX_P210 ? 2 * out_.height : out_.height * 3 / 2, out_.width, CV_MAKETYPE(CV_16U, 1));
+            else if (fo == OCTVR_PIX_UYVY422 || fo == OCTVR_PIX_YUYV422)
                 output.create(out_.height, 2 * out_.width, CV_8UC1);
             else if (fo == OCTVR_PIX_YUV422P || fo == OCTVR_PIX_NV16)
                 output.create(2 * out_.height, out_.width, CV_8UC1);
@@ -550,6 +557,8 @@ public:
     // octvr_mapper_set_pixel_formats).  OCTVR_PIX_UYVY422 (packed 4:2:2, capture and playout cards) is a
     // 2W x H CV_8U image, converted to and from 4:2:0 frames of the mapper's own by one launch each; so are
     // OCTVR_PIX_YUYV422 (2W x H), OCTVR_PIX_YUV422P and OCTVR_PIX_NV16 (W x 2H: Y over H chroma rows).
+    // The 10-bit OCTVR_PIX_P010, _YUV420P10 (W x 3H/2), _P210 and _YUV422P10 (W x 2H) are CV_16U images of 16-bit
+    // little-endian words (or CV_8U of 2W byte columns), narrowed to and widened from the mapper's 8-bit frames.
     void set_pixel_formats(int in_format, int out_format) {
         detail::check(octvr_mapper_set_pixel_formats(m_.get(), in_format, out_format));
     }

@@ -274,14 +274,41 @@ int octvr_mapper_set_frames_in_flight(octvr_mapper* mapper, int k);
  * Out-then-in is the identity, and a stitch in any of them is the planar stitch of the converted frames, bit for
  * bit.  A pitch below the row's width is OCTVR_E_INVALID before any launch.  octvr_mapper_info reports
  * "yuv422_runs", "yuv422_in_bytes" and "yuv422_out_bytes" for a side in one of these three layouts (the "uyvy_*"
- * keys stay UYVY's alone). */
+ * keys stay UYVY's alone).
+ *
+ * 10-bit frames, each valid for either side independently of the other side's format, through the same per-slot
+ * NV12 frames and footprint conversion (the stitch stays the 8-bit one).  Every sample is a 16-bit little-endian
+ * word, so a row is 2 W bytes; W, H even; `pitch` >= 2 W in bytes; the base address and the pitch are multiples
+ * of 2 (else OCTVR_E_INVALID before any launch), no other alignment is needed:
+ *   OCTVR_PIX_P010       4:2:0 semi-planar (HEVC Main10 from hardware decoders, what encoders take), W x 3H/2
+ *                        words: rows [0, H) are Y; row H + j is chroma row j as W/2 U,V word pairs.  The sample
+ *                        is in bits 15..6; the low 6 bits are ignored on input and written as 0
+ *   OCTVR_PIX_YUV420P10  4:2:0 planar (ffmpeg yuv420p10le), "Y over [U|V]" in words: row H + j holds U in words
+ *                        [0, W/2) and V in [W/2, W).  The sample is in bits 9..0; the high 6 bits are ignored on
+ *                        input (word & 0x3FF) and written as 0
+ *   OCTVR_PIX_P210       4:2:2 semi-planar, W x 2H words: H rows of Y, then H chroma rows of U,V word pairs; the
+ *                        sample in bits 15..6 as P010's
+ *   OCTVR_PIX_YUV422P10  4:2:2 planar (ffmpeg yuv422p10le), W x 2H words: row H + j holds U in words [0, W/2) and V
+ *                        in [W/2, W); the sample in bits 9..0 as YUV420P10's
+ *   in  v8 = min(255, (v10 + 2) >> 2) per sample (for P010 / P210 min(255, (word + 128) >> 8)); the 4:2:2 layouts
+ *       narrow each chroma sample first and then average the 8-bit rows, (c8[2r] + c8[2r + 1] + 1) >> 1 (10-bit
+ *       3 and 6 give 1 and 2, so 2);
+ *   out v10 = v8 << 2 (the word v8 << 8 for P010 / P210, v8 << 2 for the planar two); the 4:2:2 layouts write
+ *       chroma row r to rows 2r and 2r + 1; bytes between a row's 2 W bytes and its pitch are never written.
+ * Out-then-in is the identity, and a stitch in any of them is the planar 8-bit stitch of the frames converted by
+ * the in rule, stored by the out rule, bit for bit.  octvr_mapper_info reports "yuv10_runs", "yuv10_in_bytes" and
+ * "yuv10_out_bytes" for a side in one of these four (the "uyvy_*" and "yuv422_*" keys are then 0). */
 enum {
     OCTVR_PIX_YUV420P = 0,
     OCTVR_PIX_NV12 = 1,
     OCTVR_PIX_UYVY422 = 16,
     OCTVR_PIX_YUYV422 = 17,
     OCTVR_PIX_YUV422P = 18,
-    OCTVR_PIX_NV16 = 19
+    OCTVR_PIX_NV16 = 19,
+    OCTVR_PIX_P010 = 32,
+    OCTVR_PIX_YUV420P10 = 33,
+    OCTVR_PIX_P210 = 34,
+    OCTVR_PIX_YUV422P10 = 35
 };
 int octvr_mapper_set_pixel_formats(octvr_mapper* mapper, int in_format, int out_format);
 int octvr_mapper_pixel_formats(const octvr_mapper* mapper, int* in_format, int* out_format);
@@ -408,7 +435,13 @@ int octvr_async_info(const octvr_async* async, char* buf, size_t len);
  * planes of a push: YUYV in_planes[3*i] only (2 W bytes x H rows); YUV422P Y (W x H), U and V (W/2 bytes x H rows
  * each); NV16 Y and the U,V plane (W bytes x H rows each), the third entry is ignored.  The copy-in packs a
  * footprint run at 4 bytes per pixel of the run: its two luma rows, then its two chroma rows in the format's
- * layout.  octvr_async_push_device takes one device frame per camera in the Mapper's layout of the format. */
+ * layout.  octvr_async_push_device takes one device frame per camera in the Mapper's layout of the format.
+ * OCTVR_PIX_P010, OCTVR_PIX_YUV420P10, OCTVR_PIX_P210 and OCTVR_PIX_YUV422P10 likewise: input only (as the output
+ * format OCTVR_E_UNSUPPORTED, nothing changed).  Host planes of a push, rows of 16-bit words with even pitches and
+ * addresses: P010 / P210 Y (2 W bytes x H rows) and the U,V plane (2 W bytes x H/2 or H rows), the third entry is
+ * ignored; the planar two Y, U and V (U and V W bytes x H/2 or H rows each).  The copy-in packs a footprint run as
+ * its two luma rows, then its chroma row(s) in the format's layout: 6 bytes per pixel of the run for 4:2:0, 8 for
+ * 4:2:2.  octvr_async_push_device takes one device frame per camera in the Mapper's layout of the format. */
 int octvr_async_set_pixel_formats(octvr_async* async, int in_format, int out_format);
 int octvr_async_pixel_formats(const octvr_async* async, int* in_format, int* out_format);
 /* push(inputs, output) (async.cpp:174-189): in_planes[3*i+0/1/2] = Y, U, V host planes of input i
@@ -558,7 +591,7 @@ int octvr_debug_json_number(const char* json, int flags, double* value);
  * packed bytes, *bytes the total.  OCTVR_E_INVALID for a run outside its frame, a bad plane or a short buffer. */
 /* (For OCTVR_PIX_UYVY422 planes[3*cam] is the camera's packed plane and a run packs its two packed rows.  For
  * OCTVR_PIX_YUYV422, _YUV422P and _NV16 the planes are octvr_async_push's for the format and a run is its two luma
- * rows, then its two chroma rows.) */
+ * rows, then its two chroma rows; for the four 10-bit formats its two luma rows, then its one or two chroma rows.) */
 int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const uint32_t* runs, int n_runs,
                           const uint8_t* const* planes, const size_t* pitches, int format, uint8_t* packed, size_t cap,
                           size_t* sizes, size_t* bytes);

@@ -35,6 +35,8 @@
 //     input; device frames are converted the same way from the caller's frames;
 //   * or any other 8-bit 4:2:2 capture layout (OCTVR_PIX_YUYV422, _YUV422P, _NV16; yuv422.hip): the same table
 //     and buffers, a run packed as its two luma rows and its two chroma rows (4 B per pixel of the run too).
+//   * or a 10-bit layout (OCTVR_PIX_P010, _YUV420P10, _P210, _YUV422P10; yuv10.hip): the same pieces with the
+//     format's own offsets (6 or 8 B per pixel of the run: yuv10_run_table), narrowed into the same NV12 frames.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -57,6 +59,7 @@
 #include "mapper.hpp"
 #include "uyvy_host.hpp"
 #include "yuv422_host.hpp"
+#include "yuv10_host.hpp"
 
 using namespace octvr;
 
@@ -269,16 +272,20 @@ struct octvr_async {
     // UYVY input: the unpack kernel's pieces over the same runs with their places in the packed buffers
     // (uyvy_run_table), built when the format is first set
     // (shared by the YUYV / YUV422P / NV16 inputs: every 4:2:2 layout packs a piece into the same 4 B per pixel)
-    bool in_422() const { return in_fmt == OCTVR_PIX_UYVY422 || yuv422_format(in_fmt); }
+    // (the 10-bit layouts take the same pieces at 6 or 8 B per pixel: the table is rebuilt when uy_bpp changes)
+    bool in_422() const { return converted_format(in_fmt); }
     // the unpack launch of the input format over the table, from the packed buffer or the caller's frames
     void unpack_422(const UyvySources& src, const FootFrames& frames, hipStream_t s) {
         if (in_fmt == OCTVR_PIX_UYVY422)
             HIP_CHECK(launch_uyvy_unpack(uy_table_dev.p, (int)uy_table.size(), src, frames, s));
+        else if (yuv10_format(in_fmt))
+            HIP_CHECK(launch_yuv10_unpack(in_fmt - kYuv10First, uy_table_dev.p, (int)uy_table.size(), src, frames, s));
         else
             HIP_CHECK(launch_yuv422_unpack(in_fmt - kYuv422First, uy_table_dev.p, (int)uy_table.size(), src, frames, s));
     }
     std::vector<UyvyRun> uy_table;
     size_t uy_packed_bytes = 0;
+    int uy_bpp = 0;  // packed bytes per pixel of a piece's row the table's offsets were built with (0: no table)
     DevBuf<UyvyRun> uy_table_dev;
     Slot slots[kSlots];
     // output plane sets the caller registered (octvr_async_register_output): page-locked, downloaded into
@@ -347,6 +354,17 @@ struct octvr_async {
                         const int i = (int)(r.cam & 31u);
                         uyvy_pack_run(dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng, j.in_planes[3 * i],
                                       j.in_pitches[3 * i]);
+                    }
+                });
+                return;
+            }
+            if (yuv10_format(in_fmt)) {
+                copy_in_pool.run(uy_table.size(), [&](size_t lo, size_t hi) {
+                    for (size_t k = lo; k < hi; k++) {
+                        const UyvyRun& r = uy_table[k];
+                        const int i = (int)(r.cam & 31u);
+                        yuv10_pack_run(in_fmt - kYuv10First, dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng,
+                                       &j.in_planes[3 * i], &j.in_pitches[3 * i]);
                     }
                 });
                 return;
@@ -741,7 +759,17 @@ int octvr_async_push(octvr_async* a, const uint8_t* const* in_planes, const size
         const size_t w = (size_t)a->in_w[i];
         const int f = a->in_fmt;
         // YUV422P's planes are the planar ones (Y, U, V; h chroma rows instead of h / 2): the last branch
-        const bool bad = f == OCTVR_PIX_UYVY422 || f == OCTVR_PIX_YUYV422 ? !in_planes[3 * i] || in_pitches[3 * i] < 2 * w
+        // the 10-bit layouts: planes of 16-bit words (even addresses and pitches); P010 / P210 Y and a U,V plane of
+        // 2 w bytes a row, the planar two Y, U and V with w bytes a row of U and of V
+        auto even = [&](int k) { return yuv10_aligned(in_planes[3 * i + k], in_pitches[3 * i + k]); };
+        const bool bad = yuv10_format(f)
+                             ? (f == OCTVR_PIX_P010 || f == OCTVR_PIX_P210
+                                    ? !in_planes[3 * i] || !in_planes[3 * i + 1] || in_pitches[3 * i] < 2 * w ||
+                                          in_pitches[3 * i + 1] < 2 * w || !even(0) || !even(1)
+                                    : !in_planes[3 * i] || !in_planes[3 * i + 1] || !in_planes[3 * i + 2] ||
+                                          in_pitches[3 * i] < 2 * w || in_pitches[3 * i + 1] < w || in_pitches[3 * i + 2] < w ||
+                                          !even(0) || !even(1) || !even(2))
+                         : f == OCTVR_PIX_UYVY422 || f == OCTVR_PIX_YUYV422 ? !in_planes[3 * i] || in_pitches[3 * i] < 2 * w
                          : f == OCTVR_PIX_NV12 || f == OCTVR_PIX_NV16
                              ? !in_planes[3 * i] || !in_planes[3 * i + 1] || in_pitches[3 * i] < w || in_pitches[3 * i + 1] < w
                              : !in_planes[3 * i] || !in_planes[3 * i + 1] || !in_planes[3 * i + 2] || in_pitches[3 * i] < w ||
@@ -783,7 +811,9 @@ int octvr_async_push_device(octvr_async* a, const uint8_t* const* in_dev, const 
                 REQUIRE((uint64_t)in_pitch[i] * (uint64_t)a->in_h[i] < 0x7FFFFFFFull, "input frame too large");
                 continue;
             }
-            if (yuv422_format(a->in_fmt)) {  // a whole frame of the layout, converted by the pipeline
+            if (yuv10_format(a->in_fmt))
+                REQUIRE(yuv10_aligned(in_dev[i], in_pitch[i]), "10-bit input frames and pitches must be multiples of 2");
+            if (yuv422_format(a->in_fmt) || yuv10_format(a->in_fmt)) {  // a whole frame of the layout, converted by the pipeline
                 REQUIRE(in_pitch[i] >= frame422_row_bytes(a->in_fmt, a->in_w[i]), "4:2:2 input pitch smaller than a row of the format");
                 REQUIRE((uint64_t)in_pitch[i] * (uint64_t)frame422_rows(a->in_fmt, a->in_h[i]) < 0x7FFFFFFFull, "input frame too large");
                 continue;
@@ -909,9 +939,14 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
     return guarded([&] {
         REQUIRE(a, "NULL argument");
         auto known = [](int f) {
-            return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || f == OCTVR_PIX_UYVY422 || yuv422_format(f);
+            return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || converted_format(f);
         };
         REQUIRE(known(in_format) && known(out_format), "pixel format must be an OCTVR_PIX_* value");
+        if (yuv10_format(out_format))
+            throw OctvrError(OCTVR_E_UNSUPPORTED,
+                             "the 10-bit layouts are input formats of the pipeline only: its merge, copy-out and registered "
+                             "output planes are per-plane tables of an 8-bit 4:2:0 frame (a Mapper writes them: "
+                             "octvr_mapper_set_pixel_formats)");
         if (yuv422_format(out_format))
             throw OctvrError(OCTVR_E_UNSUPPORTED,
                              "the 4:2:2 layouts are input formats of the pipeline only: its merge, copy-out and registered "
@@ -928,10 +963,14 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
         // U and V rows together, which needs even widths (they are, since creation)
         for (int w : a->in_w) REQUIRE(w % 2 == 0, "input widths must be even");
         DeviceGuard dg0(a->device);
-        const bool in422 = in_format == OCTVR_PIX_UYVY422 || yuv422_format(in_format);
-        if (in422 && a->uy_table.empty() && !a->runs.empty()) {
+        const bool in422 = converted_format(in_format);
+        // the pieces' places in the packed buffer are the format's own: 4 bytes per pixel of a piece's row for the
+        // 8-bit 4:2:2 layouts, 6 or 8 for the 10-bit ones; a switch between them rebuilds the table
+        const int bpp = yuv10_format(in_format) ? yuv10_run_bpp(in_format - kYuv10First) : 4;
+        if (in422 && a->uy_bpp != bpp && !a->runs.empty()) {
             size_t bytes = 0;
-            std::vector<UyvyRun> t = uyvy_run_table(a->runs, a->in_w, bytes);
+            std::vector<UyvyRun> t = yuv10_format(in_format) ? yuv10_run_table(in_format - kYuv10First, a->runs, a->in_w, bytes)
+                                                             : uyvy_run_table(a->runs, a->in_w, bytes);
             REQUIRE(bytes < ((size_t)1 << 32) && t.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
             a->uy_table_dev.upload(t.data(), t.size());
             for (auto& sl : a->slots)  // 4 bytes per pixel pair row against 3: larger packed buffers
@@ -942,6 +981,7 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
                 }
             a->uy_table = std::move(t);
             a->uy_packed_bytes = bytes;
+            a->uy_bpp = bpp;
         }
         // a 4:2:2 pipeline converts once for all its mappers, which read its NV12 frames
         const int mapper_in = in422 ? OCTVR_PIX_NV12 : in_format;

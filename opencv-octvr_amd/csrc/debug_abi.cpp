@@ -24,12 +24,20 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
     return guarded([&] {
         REQUIRE(in_w && in_h && runs && planes && pitches && packed && bytes, "NULL argument");
         REQUIRE(n_inputs > 0 && n_inputs <= kMaxCams && n_runs >= 0, "bad counts");
-        REQUIRE(format == OCTVR_PIX_YUV420P || format == OCTVR_PIX_NV12 || format == OCTVR_PIX_UYVY422 || yuv422_format(format),
+        REQUIRE(format == OCTVR_PIX_YUV420P || format == OCTVR_PIX_NV12 || converted_format(format),
                 "pixel format must be an OCTVR_PIX_* value");
         const bool nv12 = format == OCTVR_PIX_NV12, uyvy = format == OCTVR_PIX_UYVY422, y422 = yuv422_format(format);
+        const bool y10 = yuv10_format(format);
         for (int i = 0; i < n_inputs; i++) {
             const size_t w = (size_t)in_w[i];
             REQUIRE(in_w[i] > 0 && in_h[i] > 0 && in_w[i] % 2 == 0 && in_h[i] % 2 == 0, "input sizes must be even");
+            if (y10) {  // planes of 16-bit words: Y and U,V pairs of 2 w bytes per row, or Y, U and V (w bytes per row)
+                const bool semi = format == OCTVR_PIX_P010 || format == OCTVR_PIX_P210;
+                REQUIRE(planes[3 * i] && planes[3 * i + 1] && pitches[3 * i] >= 2 * w && pitches[3 * i + 1] >= (semi ? 2 * w : w),
+                        "bad input plane");
+                REQUIRE(semi || (planes[3 * i + 2] && pitches[3 * i + 2] >= w), "bad input plane");
+                continue;
+            }
             if (uyvy || format == OCTVR_PIX_YUYV422) {  // one packed plane of 2 w bytes per row
                 REQUIRE(planes[3 * i] && pitches[3 * i] >= 2 * w, "bad input plane");
                 continue;
@@ -51,9 +59,11 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
             const int w = in_w[cam], h = in_h[cam];
             REQUIRE(rp < (uint32_t)h / 2 && ng > 0 && g0 < (uint32_t)(w + 7) / 8 && ng <= (uint32_t)(w + 7) / 8 - g0,
                     "run outside its frame");
-            const size_t n = (uyvy || y422 ? 4 : 3) * (size_t)run_luma_bytes(w, (int)g0, (int)ng);
+            const size_t n = (y10 ? yuv10_run_bpp(format - kYuv10First) : uyvy || y422 ? 4 : 3) * (size_t)run_luma_bytes(w, (int)g0, (int)ng);
             REQUIRE(off + n <= cap, "buffer too small");
-            const size_t got = uyvy   ? uyvy_pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes[3 * cam], pitches[3 * cam])
+            const size_t got = y10    ? yuv10_pack_run(format - kYuv10First, packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam,
+                                                       pitches + 3 * cam)
+                               : uyvy ? uyvy_pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes[3 * cam], pitches[3 * cam])
                                : y422 ? yuv422_pack_run(format - kYuv422First, packed + off, w, (int)rp, (int)g0, (int)ng,
                                                         planes + 3 * cam, pitches + 3 * cam)
                                       : pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam, nv12);

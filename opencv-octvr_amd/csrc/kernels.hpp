@@ -315,6 +315,13 @@ hipError_t launch_uyvy_pack(const uint8_t* src, int w, int h, uint8_t* out, size
 hipError_t launch_yuv422_unpack(int layout, const UyvyRun* table, int n_pieces, const UyvySources& src,
                                 const FootFrames& frames, hipStream_t s);
 hipError_t launch_yuv422_pack(int layout, const uint8_t* src, int w, int h, uint8_t* out, size_t pitch, hipStream_t s);
+// The 10-bit layouts (OCTVR_PIX_P010 / YUV420P10 / P210 / YUV422P10, yuv10.hip; `layout` is yuv10_host.hpp's
+// Yuv10Layout): the same table pieces, sources and 8-bit NV12 frames.  A frame source is the caller's whole frame
+// of 16-bit words (3 h / 2 or 2 h rows, pitch >= 2 w, base and pitch even), the packed buffer holds
+// yuv10_pack_run's pieces at the offsets of yuv10_run_table.  The pack writes no byte of a row past 2 w.
+hipError_t launch_yuv10_unpack(int layout, const UyvyRun* table, int n_pieces, const UyvySources& src,
+                               const FootFrames& frames, hipStream_t s);
+hipError_t launch_yuv10_pack(int layout, const uint8_t* src, int w, int h, uint8_t* out, size_t pitch, hipStream_t s);
 
 struct TiledLut {
     const TileHdr* meta;          // per staged item kMetaWords 16-byte words: the TileHdr, then kTileSlots TileSlots

@@ -90,8 +90,9 @@ void check_out_pitch(const octvr_mapper* m, size_t out_pitch) {
         REQUIRE((uint64_t)out_pitch * (uint64_t)m->SH < 0x7FFFFF80ull, "output frame larger than 2 GiB");
         return;
     }
-    if (m->uy_out) {  // YUYV: SH rows of 2 SW bytes; YUV422P and NV16: 2 SH rows of SW bytes
+    if (m->uy_out) {  // YUYV: SH rows of 2 SW bytes; YUV422P and NV16: 2 SH rows of SW bytes; 10-bit: rows of 2 SW bytes
         REQUIRE(out_pitch >= frame422_row_bytes(m->fmt422_out, m->SW), "4:2:2 output pitch smaller than a row of the format");
+        REQUIRE(!yuv10_format(m->fmt422_out) || (out_pitch & 1) == 0, "10-bit output pitch must be a multiple of 2");
         REQUIRE((uint64_t)out_pitch * (uint64_t)frame422_rows(m->fmt422_out, m->SH) < 0x7FFFFF80ull, "output frame larger than 2 GiB");
         return;
     }
@@ -119,6 +120,8 @@ UyvySources uyvy_sources(const octvr_mapper* m, const uint8_t* const* in_dev, co
             REQUIRE((uint64_t)in_pitch[i] * (uint64_t)m->in_h[i] < 0x7FFFFFFFull, "input frame larger than 2 GiB");
         } else {
             REQUIRE(in_pitch[i] >= frame422_row_bytes(m->fmt422_in, m->in_w[i]), "4:2:2 input pitch smaller than a row of the format");
+            REQUIRE(!yuv10_format(m->fmt422_in) || yuv10_aligned(in_dev[i], in_pitch[i]),
+                    "10-bit input frames and pitches must be multiples of 2");
             REQUIRE((uint64_t)in_pitch[i] * (uint64_t)frame422_rows(m->fmt422_in, m->in_h[i]) < 0x7FFFFFFFull,
                     "input frame larger than 2 GiB");
         }
@@ -133,6 +136,8 @@ UyvySources uyvy_sources(const octvr_mapper* m, const uint8_t* const* in_dev, co
 void pack_422(const octvr_mapper* m, const uint8_t* src, uint8_t* out, size_t pitch, hipStream_t s) {
     if (m->fmt422_out == OCTVR_PIX_UYVY422)
         HIP_CHECK(launch_uyvy_pack(src, m->SW, m->SH, out, pitch, s));
+    else if (yuv10_format(m->fmt422_out))
+        HIP_CHECK(launch_yuv10_pack(m->fmt422_out - kYuv10First, src, m->SW, m->SH, out, pitch, s));
     else
         HIP_CHECK(launch_yuv422_pack(m->fmt422_out - kYuv422First, src, m->SW, m->SH, out, pitch, s));
 }
@@ -140,6 +145,8 @@ void pack_422(const octvr_mapper* m, const uint8_t* src, uint8_t* out, size_t pi
 FrameSet uyvy_unpack_slot(const octvr_mapper* m, const octvr_mapper::FrameSlot& sl, const UyvySources& us, hipStream_t s) {
     if (m->fmt422_in == OCTVR_PIX_UYVY422)
         HIP_CHECK(launch_uyvy_unpack(m->uy_table.p, (int)m->uy_table.n, us, *sl.uy_in, s));
+    else if (yuv10_format(m->fmt422_in))  // the table's offsets are not read: the sources are frames
+        HIP_CHECK(launch_yuv10_unpack(m->fmt422_in - kYuv10First, m->uy_table.p, (int)m->uy_table.n, us, *sl.uy_in, s));
     else
         HIP_CHECK(launch_yuv422_unpack(m->fmt422_in - kYuv422First, m->uy_table.p, (int)m->uy_table.n, us, *sl.uy_in, s));
     FrameSet fs;
@@ -367,6 +374,7 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
         }
     }
     check_out_pitch(m, out_pitch);
+    REQUIRE(!(m->uy_out && yuv10_format(m->fmt422_out)) || yuv10_aligned(out_dev, 0), "10-bit output frame must be 2-byte aligned");
     DeviceGuard dg(m->device);
     // packed UYVY sides: the slot's unpack launch fills its 4:2:0 input frames, which every stage below reads,
     // and the stitch writes the slot's 4:2:0 output frame, which the pack launch converts at the end
@@ -447,6 +455,8 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
     REQUIRE((int)m->slots.size() >= nb, "a batch of n frames needs n frames in flight (octvr_mapper_set_frames_in_flight)");
     REQUIRE(nb <= 2 || m->nc <= 16, "a batch of 4 frames holds 16 cameras per frame (inputs and overlays)");
     check_out_pitch(m, out_pitch);
+    for (int f = 0; f < nb; f++)
+        REQUIRE(!(m->uy_out && yuv10_format(m->fmt422_out)) || yuv10_aligned(out_dev[f], 0), "10-bit output frame must be 2-byte aligned");
     DeviceGuard dg(m->device);
     FrameSet fs[kMaxBatch];  // every frame checked before any of them puts work on the stream
     UyvySources us[kMaxBatch];

@@ -9,6 +9,7 @@
 #include "host_common.hpp"
 #include "uyvy_host.hpp"
 #include "yuv422_host.hpp"
+#include "yuv10_host.hpp"
 
 // =================================================================================================
 // Mapper (vr::Mapper)
@@ -88,7 +89,8 @@ struct octvr_mapper {
     // frames (`pix` carries NV12 for that side); uy_table: the unpack kernel's pieces over this mapper's footprint
     // The other 4:2:2 layouts (YUYV, YUV422P, NV16; yuv422.hip) share all of it — the slot frames, the table, the
     // footprint runs: uy_in / uy_out say that the side is 4:2:2, fmt422_in / fmt422_out which layout
-    // (OCTVR_PIX_UYVY422 .. OCTVR_PIX_NV16; 0: the side is 4:2:0)
+    // (OCTVR_PIX_UYVY422 .. OCTVR_PIX_NV16; 0: the side is 4:2:0).  So do the 10-bit layouts (OCTVR_PIX_P010 ..
+    // OCTVR_PIX_YUV422P10; yuv10.hip): a converted side like a 4:2:2 one, 4:2:0 or not
     bool uy_in = false, uy_out = false;
     int fmt422_in = 0, fmt422_out = 0;
     DevBuf<octvr::UyvyRun> uy_table;
@@ -130,11 +132,21 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
 void mapper_prepare_preview(octvr_mapper* m, const octvr_rig* rig, int w, int h);
 // The packed UYVY sides (octvr_mapper_set_pixel_formats): allocates or frees every frame slot's 4:2:0 frames and
 // builds the unpack table from the mapper's footprint.  The mapper is synchronized by the caller.
-// in / out: the side's 4:2:2 format (OCTVR_PIX_UYVY422, _YUYV422, _YUV422P, _NV16) or 0 for a 4:2:0 side.
+// in / out: the side's converted format (OCTVR_PIX_UYVY422, _YUYV422, _YUV422P, _NV16, or a 10-bit one) or 0 for
+// an 8-bit 4:2:0 side.
 void mapper_set_uyvy(octvr_mapper* m, int in, int out);
-// Bytes of a row and rows of a w x h frame in a 4:2:2 format.
-inline size_t frame422_row_bytes(int fmt, int w) { return (fmt == OCTVR_PIX_UYVY422 || fmt == OCTVR_PIX_YUYV422 ? 2 : 1) * (size_t)w; }
-inline size_t frame422_rows(int fmt, int h) { return (fmt == OCTVR_PIX_UYVY422 || fmt == OCTVR_PIX_YUYV422 ? 1 : 2) * (size_t)h; }
+// A format whose side is converted to or from the slot's NV12 frames.
+inline bool converted_format(int f) { return f == OCTVR_PIX_UYVY422 || octvr::yuv422_format(f) || octvr::yuv10_format(f); }
+// Bytes of a row and rows of a w x h frame in a 4:2:2 or 10-bit format.
+inline size_t frame422_row_bytes(int fmt, int w) {
+    return (fmt == OCTVR_PIX_UYVY422 || fmt == OCTVR_PIX_YUYV422 || octvr::yuv10_format(fmt) ? 2 : 1) * (size_t)w;
+}
+inline size_t frame422_rows(int fmt, int h) {
+    if (octvr::yuv10_format(fmt)) return (size_t)octvr::yuv10_frame_rows(fmt - octvr::kYuv10First, h);
+    return (fmt == OCTVR_PIX_UYVY422 || fmt == OCTVR_PIX_YUYV422 ? 1 : 2) * (size_t)h;
+}
+// A 10-bit frame's samples are 16-bit words: its base and pitch are multiples of 2.
+inline bool yuv10_aligned(const void* base, size_t pitch) { return ((reinterpret_cast<uintptr_t>(base) | pitch) & 1u) == 0; }
 // Consecutive set groups of a footprint as runs, gaps of up to `gap` groups bridged; bytes: their 4:2:0 size.
 constexpr int kRunGap = 2;
 std::vector<FootRun> footprint_runs(const SourceFootprint& f, size_t& bytes, int gap = kRunGap);

@@ -382,16 +382,17 @@ int octvr_mapper_set_pixel_formats(octvr_mapper* m, int in_format, int out_forma
     return guarded([&] {
         REQUIRE(m, "NULL argument");
         auto known = [](int f) {
-            return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || f == OCTVR_PIX_UYVY422 || yuv422_format(f);
+            return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || converted_format(f);
         };
         REQUIRE(known(in_format) && known(out_format),
                 "pixel format must be OCTVR_PIX_YUV420P, OCTVR_PIX_NV12, OCTVR_PIX_UYVY422, OCTVR_PIX_YUYV422, "
-                "OCTVR_PIX_YUV422P or OCTVR_PIX_NV16");
+                "OCTVR_PIX_YUV422P, OCTVR_PIX_NV16, OCTVR_PIX_P010, OCTVR_PIX_YUV420P10, OCTVR_PIX_P210 or "
+                "OCTVR_PIX_YUV422P10");
         DeviceGuard dg(m->device);
         mapper_sync(*m);  // stitches in flight keep the layouts they were issued with
         // a packed UYVY side is converted to or from NV12 frames of the frame slot: the stitch sees NV12 there
-        // (so is a side in any other 4:2:2 layout)
-        auto is422 = [](int f) { return f == OCTVR_PIX_UYVY422 || yuv422_format(f); };
+        // (so is a side in any other 4:2:2 layout, or in a 10-bit one)
+        auto is422 = [](int f) { return converted_format(f); };
         mapper_set_uyvy(m, is422(in_format) ? in_format : 0, is422(out_format) ? out_format : 0);
         m->pix = (in_format != OCTVR_PIX_YUV420P ? kPixInNv12 : 0) | (out_format != OCTVR_PIX_YUV420P ? kPixOutNv12 : 0);
     });
@@ -517,10 +518,17 @@ int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
               ", \"uyvy_in_bytes\": " + std::to_string(uy_i ? m->uy_in_bytes : 0) +
               ", \"uyvy_out_bytes\": " + std::to_string(uy_o ? (size_t)2 * m->SW * m->SH : 0);
         // the same three figures for a YUYV, YUV422P or NV16 side (every 4:2:2 layout is 2 bytes per pixel)
-        const bool y2_i = m->uy_in && !uy_i, y2_o = m->uy_out && !uy_o;
+        const bool y2_i = m->uy_in && yuv422_format(m->fmt422_in), y2_o = m->uy_out && yuv422_format(m->fmt422_out);
         js += ", \"yuv422_runs\": " + std::to_string(y2_i ? m->uy_runs : 0) +
               ", \"yuv422_in_bytes\": " + std::to_string(y2_i ? m->uy_in_bytes : 0) +
               ", \"yuv422_out_bytes\": " + std::to_string(y2_o ? (size_t)2 * m->SW * m->SH : 0);
+        // a 10-bit side: 6 (4:2:0) or 8 (4:2:2) bytes per pixel of a footprint piece's row against UYVY's 4, and
+        // 3 or 4 bytes per output pixel
+        const bool t_i = m->uy_in && yuv10_format(m->fmt422_in), t_o = m->uy_out && yuv10_format(m->fmt422_out);
+        js += ", \"yuv10_runs\": " + std::to_string(t_i ? m->uy_runs : 0) + ", \"yuv10_in_bytes\": " +
+              std::to_string(t_i ? m->uy_in_bytes / 4 * (size_t)yuv10_run_bpp(m->fmt422_in - kYuv10First) : 0) +
+              ", \"yuv10_out_bytes\": " +
+              std::to_string(t_o ? (size_t)2 * m->SW * frame422_rows(m->fmt422_out, m->SH) : 0);
         if (m->mb) js += ", " + multiband_info(*m->mb);
         else if (!m->tiles.stats.empty()) js += ", " + m->tiles.stats + ", \"items_packed\": " + std::to_string(m->tiles.n_packed);
         js += "}";

@@ -226,7 +226,9 @@ def _plane_args(plane_sets):
         if len(tri) not in (1, 2, 3):
             raise ValueError("a plane set is (Y, U, V), (Y, UV) for an NV12 side or (UYVY,) for a packed 4:2:2 input")
         tri += [None] * (3 - len(tri))
-        for p in tri:
+        for k, p in enumerate(tri):
+            if p is not None and p.dtype == np.uint16 and p.ndim == 2 and p.strides[1] == 2:
+                p = tri[k] = p.view(np.uint8)  # a plane of 16-bit words (the 10-bit formats) as its bytes
             if p is not None:
                 assert p.dtype == np.uint8 and p.ndim == 2 and p.strides[1] == 1, \
                     "uint8 2-D planes with unit column stride"
@@ -245,7 +247,7 @@ def debug_pack_runs(in_sizes, runs, planes, fmt="yuv420p"):
     h = (C.c_int * n)(*[s[1] for s in in_sizes])
     r = np.ascontiguousarray(np.asarray(runs, np.uint32).reshape(-1, 4))
     ptr, pitch, keep = _plane_args(planes)
-    cap = int(sum(4 * 8 * int(x[3]) for x in r)) + 8
+    cap = int(sum(8 * 8 * int(x[3]) for x in r)) + 8
     packed = np.full(cap, 0x5A, np.uint8)
     sizes = np.zeros(len(r), np.uintp)
     total = C.c_size_t()
@@ -504,24 +506,33 @@ class BatchRefs:
 
 PIX_YUV420P, PIX_NV12, PIX_UYVY422 = 0, 1, 16  # OCTVR_PIX_*
 PIX_YUYV422, PIX_YUV422P, PIX_NV16 = 17, 18, 19  # the other 8-bit 4:2:2 capture layouts
+PIX_P010, PIX_YUV420P10, PIX_P210, PIX_YUV422P10 = 32, 33, 34, 35  # 10-bit samples in 16-bit little-endian words
 PIX_NAMES = ("yuv420p", "nv12")  # the 4:2:0 layouts, by value
 _PIX_BY_NAME = {"yuv420p": PIX_YUV420P, "nv12": PIX_NV12, "uyvy422": PIX_UYVY422, "yuyv422": PIX_YUYV422,
-                "yuv422p": PIX_YUV422P, "nv16": PIX_NV16}
+                "yuv422p": PIX_YUV422P, "nv16": PIX_NV16, "p010": PIX_P010, "yuv420p10": PIX_YUV420P10,
+                "p210": PIX_P210, "yuv422p10": PIX_YUV422P10}
+_PIX_10BIT = (PIX_P010, PIX_YUV420P10, PIX_P210, PIX_YUV422P10)
 _PIX_BY_VALUE = {v: k for k, v in _PIX_BY_NAME.items()}
 
 
 def _pix_value(fmt):
     if isinstance(fmt, str):
         if fmt.lower() not in _PIX_BY_NAME:
-            raise ValueError("pixel format must be 'yuv420p', 'nv12', 'uyvy422', 'yuyv422', 'yuv422p' or 'nv16'")
+            raise ValueError("pixel format must be 'yuv420p', 'nv12', 'uyvy422', 'yuyv422', 'yuv422p', 'nv16', "
+                             "'p010', 'yuv420p10', 'p210' or 'yuv422p10'")
         return _PIX_BY_NAME[fmt.lower()]
     return int(fmt)  # the library rejects unknown values (OCTVR_E_INVALID)
 
 
 def frame_shape(fmt, w, h):
     """(rows, columns) of a w x h frame in `fmt`: (3h/2, w) for the 4:2:0 layouts, (h, 2w) for "uyvy422" and
-    "yuyv422", (2h, w) for "yuv422p" and "nv16"."""
+    "yuyv422", (2h, w) for "yuv422p" and "nv16".  The 10-bit layouts in bytes (a sample is a 16-bit little-endian
+    word): (3h/2, 2w) for "p010" and "yuv420p10", (2h, 2w) for "p210" and "yuv422p10"."""
     v = _pix_value(fmt)
+    if v in (PIX_P010, PIX_YUV420P10):
+        return (int(h) * 3 // 2, 2 * int(w))
+    if v in (PIX_P210, PIX_YUV422P10):
+        return (2 * int(h), 2 * int(w))
     if v in (PIX_UYVY422, PIX_YUYV422):
         return (int(h), 2 * int(w))
     if v in (PIX_YUV422P, PIX_NV16):
@@ -653,6 +664,58 @@ def yuv420p_from_yuv422(fmt, frame, w, h):
     return out
 
 
+def _yuv10_layout(fmt):
+    v = _pix_value(fmt)
+    if v not in _PIX_10BIT:
+        raise ValueError("not a 10-bit layout")
+    return v, v in (PIX_P210, PIX_YUV422P10), v in (PIX_YUV420P10, PIX_YUV422P10)
+
+
+def yuv10_from_yuv420p(fmt, frame, w, h):
+    """The frame in the 10-bit layout `fmt` ("p010", "yuv420p10", "p210", "yuv422p10" or the PIX_* value) of an 8-bit
+    "Y over [U|V]" frame by the library's output rule: v10 = v8 << 2 (the word v8 << 8 for "p010" / "p210", v8 << 2
+    for the planar two), the 4:2:2 layouts with chroma row r on rows 2r and 2r + 1.  A uint16 array of
+    frame_shape(fmt, w, h)[0] rows and w words; .view(numpy.uint8) is the frame in bytes."""
+    v, c422, planar = _yuv10_layout(fmt)
+    f, w, h = _chroma_frame(frame, w, h)
+    u, vv = f[h:, :w // 2], f[h:, w // 2:w]
+    if c422:
+        u, vv = np.repeat(u, 2, axis=0), np.repeat(vv, 2, axis=0)
+    out = np.empty((frame_shape(v, w, h)[0], w), np.uint16)
+    out[:h] = f[:h, :w]
+    if planar:
+        out[h:, :w // 2], out[h:, w // 2:] = u, vv
+    else:
+        out[h:, 0::2], out[h:, 1::2] = u, vv
+    return out << (2 if planar else 8)
+
+
+def yuv420p_from_yuv10(fmt, frame, w, h):
+    """The 8-bit "Y over [U|V]" frame of a frame in the 10-bit layout `fmt` (uint16 words, or uint8 with two columns
+    per word; columns past a row's width are dropped) by the library's input rule: v8 = min(255, (v10 + 2) >> 2) per
+    sample, v10 bits 15..6 of a "p010" / "p210" word and bits 9..0 of a planar one; the 4:2:2 layouts then take
+    (c8[2r] + c8[2r + 1] + 1) >> 1 of the narrowed chroma rows 2r and 2r + 1."""
+    v, c422, planar = _yuv10_layout(fmt)
+    f = np.asarray(frame)
+    w, h = int(w), int(h)
+    if w <= 0 or h <= 0 or (w & 1) or (h & 1):
+        raise ValueError("10-bit frames have even width and height")
+    if f.ndim == 2 and f.dtype == np.uint8 and f.shape[1] % 2 == 0:
+        f = np.ascontiguousarray(f).view(np.uint16)
+    rows = frame_shape(v, w, h)[0]
+    if f.ndim != 2 or f.dtype != np.uint16 or f.shape[0] != rows or f.shape[1] < w:
+        raise ValueError("expected a frame of %d rows and at least %d 16-bit words a row" % (rows, w))
+    v10 = (f[:, :w] & 0x3FF if planar else f[:, :w] >> 6).astype(np.int32)
+    v8 = np.minimum(255, (v10 + 2) >> 2)
+    c = v8[h:]
+    u, vv = (c[:, :w // 2], c[:, w // 2:]) if planar else (c[:, 0::2], c[:, 1::2])
+    if c422:
+        u, vv = (u[0::2] + u[1::2] + 1) >> 1, (vv[0::2] + vv[1::2] + 1) >> 1
+    out = np.empty((h * 3 // 2, w), np.uint8)
+    out[:h], out[h:, :w // 2], out[h:, w // 2:] = v8[:h], u, vv
+    return out
+
+
 class Mapper:
     """vr::Mapper on one device: stitch(inputs YUV420P, output YUV420P) with optional gain.
 
@@ -761,13 +824,17 @@ class Mapper:
         "yuv420p" ("Y over [U|V]", the default), "nv12" (chroma rows of U,V byte pairs), "uyvy422" (packed
         4:2:2, h rows of 2w bytes, converted to and from 4:2:0 frames of the mapper's own by one launch each),
         "yuyv422" (packed, Y0 U0 Y1 V0), "yuv422p" or "nv16" (2h rows of w bytes: Y over h chroma rows, [U|V]
-        halves or U,V pairs; frame_shape gives each layout's shape), or the OCTVR_PIX_* values
-        (octvr_mapper_set_pixel_formats).  Synchronizes."""
+        halves or U,V pairs; frame_shape gives each layout's shape), the 10-bit "p010", "yuv420p10", "p210" or
+        "yuv422p10" (16-bit little-endian words, rows of 2w bytes, base and pitch multiples of 2; narrowed to and
+        widened from the mapper's 8-bit frames by v8 = min(255, (v10 + 2) >> 2) and v10 = v8 << 2: the stitch stays
+        the 8-bit one; uint8 tensors of frame_shape, e.g. a uint16 tensor's .view(torch.uint8)), or the OCTVR_PIX_*
+        values (octvr_mapper_set_pixel_formats).  Synchronizes."""
         _check(_lib.octvr_mapper_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
 
     @property
     def pixel_formats(self):
-        """(input layout, output layout) as "yuv420p" / "nv12" / "uyvy422" / "yuyv422" / "yuv422p" / "nv16"."""
+        """(input layout, output layout) as "yuv420p" / "nv12" / "uyvy422" / "yuyv422" / "yuv422p" / "nv16" / "p010" /
+        "yuv420p10" / "p210" / "yuv422p10"."""
         a, b = C.c_int(), C.c_int()
         _check(_lib.octvr_mapper_pixel_formats(self._h, C.byref(a), C.byref(b)))
         return _PIX_BY_VALUE[a.value], _PIX_BY_VALUE[b.value]
@@ -930,9 +997,11 @@ class AsyncMultiMapper:
         frame; a side that is NV12 takes (Y, UV) — UV the interleaved plane of W bytes x H/2 rows — with an
         optional third entry that is ignored.  4:2:2 inputs (set_pixel_formats): "uyvy422" / "yuyv422" one packed
         plane (h rows of 2w bytes), as a one-tuple or the array itself; "yuv422p" (Y, U, V) with U and V of h rows
-        of w/2 bytes; "nv16" (Y, UV) with UV of h rows of w bytes.  The arrays are kept alive until the matching
-        pop()."""
-        fix = lambda p: p if p is None or p.strides[1] == 1 else np.ascontiguousarray(p)
+        of w/2 bytes; "nv16" (Y, UV) with UV of h rows of w bytes.  10-bit inputs, planes of 16-bit words given as
+        uint16 arrays or as their bytes (uint8, even pitches): "p010" / "p210" (Y, UV) with Y of h rows of w words
+        and UV of h/2 or h rows of w words (U,V pairs); "yuv420p10" / "yuv422p10" (Y, U, V) with U and V of h/2 or
+        h rows of w/2 words.  The arrays are kept alive until the matching pop()."""
+        fix = lambda p: p if p is None or p.strides[1] == p.itemsize else np.ascontiguousarray(p)
         inputs = [(tri,) if isinstance(tri, np.ndarray) else tuple(tri) for tri in inputs]  # a packed UYVY plane
         ip, ipt, planes = _plane_args([tuple(fix(p) for p in tri) for tri in inputs])
         op, opt, _ = _plane_args([output])
@@ -959,7 +1028,8 @@ class AsyncMultiMapper:
         pitch, so views of larger tensors work.  ready: a recorded torch.cuda.Event the stitch waits for before
         it reads the inputs; None: the inputs are complete (synchronize the stream that wrote them first).
         The tensors are kept alive until the matching pop(), which returns `output` once the merged frame is
-        complete on the device."""
+        complete on the device.  With a 10-bit input format the inputs are uint8 tensors of frame_shape(fmt, w, h)
+        (rows of 2w bytes; a uint16 tensor's .view(torch.uint8)) at even addresses and pitches."""
         if len(inputs) != self.n:
             raise ValueError("push_device takes %d frames (every input, then every overlay), got %d"
                              % (self.n, len(inputs)))
@@ -1011,7 +1081,8 @@ class AsyncMultiMapper:
         takes one packed plane (h rows of 2w bytes) per camera, as a one-tuple or the array itself, and
         push_device one packed cuda tensor per camera; as the output format it is E_UNSUPPORTED.  "yuyv422",
         "yuv422p" and "nv16" likewise: input only, planes as push() describes, push_device one cuda tensor of
-        frame_shape(fmt, w, h) per camera."""
+        frame_shape(fmt, w, h) per camera.  So are the 10-bit "p010", "yuv420p10", "p210" and "yuv422p10": one
+        narrowing conversion per frame serves all mappers, which read the pipeline's 8-bit NV12 frames."""
         _check(_lib.octvr_async_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
 
     @property
