@@ -123,6 +123,15 @@ def frames_of(t, kind, seed=0):
     from octvr_amd import synthetic
     if kind == "smooth":  # estimated gains
         return [synthetic.smooth_yuv_frame(w, h, 3100 + seed + i) for i, (w, h) in enumerate(t["sizes"])], None
+    if kind == "contrast":  # 0 / 255 luma checkerboards of period 1, 2, 4 px per camera, chroma 128; gains 1
+        frames = []
+        for i, (w, h) in enumerate(t["sizes"]):
+            yy, xx = np.mgrid[0:h, 0:w]
+            per = 1 << (i + seed) % 3
+            f = np.full((h * 3 // 2, w), 128, np.uint8)
+            f[:h] = ((xx // per + yy // per + seed) & 1) * 255
+            frames.append(f)
+        return frames, [1.0] * t["n"]
     frames = [O.rand_img(w, h * 3 // 2, 1, 7700 + seed + i) for i, (w, h) in enumerate(t["sizes"])]
     return frames, ([1.0 + 0.012 * k * (-1) ** k for k in range(t["n"])] if t["n"] > 1 else None)
 
@@ -211,13 +220,14 @@ def check_rects(info, t, blend):
     return arr
 
 
-def stitch_case(ox, name, blend, kind, scale=None, out_fmt="yuv420p", remap="remap"):
-    """One stitch of geometry `name` against the oracle: (info, align_result_roi, got, want)."""
+def stitch_case(ox, name, blend, kind, scale=None, out_fmt="yuv420p", remap="remap", rig=None, case=None, mt=None):
+    """One stitch of geometry `name` against the oracle: (info, align_result_roi, got, want).  rig, case, mt:
+    the rig's arrays, its oracle_case and its template where they are not make_rig(name)'s (other seams)."""
     import torch
     from test_gpu_nv12 import check
-    t = make_rig(name)
-    frames, gains, want, g_orc = oracle_case(name, blend, kind, scale, remap == "texture")
-    m = ox.Mapper(template(ox, t), t["sizes"], blend=blend, enable_gain=True, scale_output=scale, remap=remap)
+    t = rig or make_rig(name)
+    frames, gains, want, g_orc = case or oracle_case(name, blend, kind, scale, remap == "texture")
+    m = ox.Mapper(mt or template(ox, t), t["sizes"], blend=blend, enable_gain=True, scale_output=scale, remap=remap)
     if out_fmt != "yuv420p":
         m.set_pixel_formats("yuv420p", out_fmt)
     info = m.info()
