@@ -508,9 +508,16 @@ typedef struct octvr_fastmapper octvr_fastmapper;
 int octvr_fastmapper_create(const octvr_rig* rig, int device, int n_inputs, const int* in_w, const int* in_h,
                             octvr_fastmapper** fastmapper);
 /* FastMapper::stitch_nv12 (mapper_fast.cpp:153-195) on device NV12 frames (H rows of Y, then H/2 rows
- * of interleaved U,V; W <= pitch < 2^24).  Output: W x 3H/2, chroma rows interleaved V,U — the reference's
+ * of interleaved U,V).  Output: W x 3H/2, chroma rows interleaved V,U — the reference's
  * channel order (merge of the V-then-U accumulators).  Stream-ordered; the FastMapper keeps no per-call
- * device state, so calls with their own outputs may run concurrently on different streams. */
+ * device state, so calls with their own outputs may run concurrently on different streams.
+ * Frames, as for the Mapper: an input of width w and height h at any base address (no alignment) and any
+ * pitch with w <= pitch < 2^24, no pitch alignment; pitch * 3h/2 bytes must be readable from the base (the
+ * kernels read the padding of a row, never past that size) and be at least 8 (a contiguous 2 x 2 frame is
+ * refused: "input frame below 8 bytes").  The output at any base address and any out_pitch >= W; bytes of
+ * a row past W are not written, and every byte of the W x 3H/2 window is (0 where no input has weight).
+ * A frame that breaks these is refused with OCTVR_E_INVALID before anything is launched
+ * (tests/test_gpu_fastmapper_layouts.py pins all of this on the GPU). */
 int octvr_fastmapper_stitch_nv12(octvr_fastmapper* fastmapper, const uint8_t* const* in_dev, const size_t* in_pitch,
                                  uint8_t* out_dev, size_t out_pitch, void* stream);
 /* Algorithmic bytes one stitch_nv12 moves (entries read, output written, source bytes its weighted taps
@@ -558,7 +565,9 @@ int octvr_debug_project_f64(const char* json, int out_w, int out_h, int input, i
  * index fast_y_kernel / fast_uv_kernel derive for every run, camera group, slot and lane — block, entry,
  * weight and header indices against the uploaded arrays, camera against the frame set, each 8-byte tap-row
  * load against an NV12 frame of pitch w + pitch_pad, the in-image taps' bytes inside the loaded 8, the
- * output bytes.  Writes per-plane counts as JSON; returns OCTVR_E_INVALID if any access is out of range. */
+ * output bytes.  Writes per-plane counts as JSON; returns OCTVR_E_INVALID if any access is out of range.
+ * Addresses are replayed relative to the frame's base: the kernels form the same offsets whatever the base,
+ * so a base off 4-byte alignment (unaligned 8-byte loads) is covered by the GPU tests only. */
 int octvr_debug_fastmapper_audit(const octvr_rig* rig, int n_inputs, const int* in_w, const int* in_h, int force_wide,
                                  int pitch_pad, char* json, size_t len);
 /* The blend = 0 composite's tiling on the host only (no GPU): the copy chain's winner per output pixel,

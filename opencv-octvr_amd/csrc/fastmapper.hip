@@ -118,7 +118,9 @@ __device__ __forceinline__ void fast_group(uint32_t fbase, const bool (&live)[kF
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(f.yuv), 0, (int)size, 0x00020000);
         const int sx = sxk[k], sy = syk[k];
         const int xa = INNER ? sx : min(max(sx, 0), sw - 1);
-        const uint32_t bx = (uint32_t)xa * bpp & ~3u;  // 4-byte aligned row start
+        // row start, 4-byte aligned relative to the frame's base: with a base or pitch off 4-byte alignment the
+        // 8-byte load itself is unaligned, which gfx950 serves (tests/test_gpu_fastmapper_layouts.py)
+        const uint32_t bx = (uint32_t)xa * bpp & ~3u;
 #pragma unroll
         for (int r = 0; r < 2; r++) {
             const int y = INNER ? sy + r : min(max(sy + r, 0), sh - 1);

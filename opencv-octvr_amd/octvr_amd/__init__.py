@@ -316,7 +316,9 @@ def debug_json_number(text, exact=True):
 def debug_fastmapper_audit(mt, in_sizes, wide=False, pitch_pad=0):
     """(ok, report): the host replay of every index the FastMapper kernels derive for this template and
     these input sizes, in the compact or (wide=True) 8-byte entry format (octvr_debug_fastmapper_audit;
-    no GPU).  report: per plane ("y", "uv") the counts and the first violation."""
+    no GPU).  report: per plane ("y", "uv") the counts and the first violation.  Every input frame is taken at
+    pitch w + pitch_pad; addresses are replayed relative to the frame's base, so a base that is not 4-byte
+    aligned is covered by the GPU test only (tests/test_gpu_fastmapper_layouts.py)."""
     n = len(in_sizes)
     w = (C.c_int * n)(*[s[0] for s in in_sizes])
     h = (C.c_int * n)(*[s[1] for s in in_sizes])
