@@ -29,14 +29,11 @@
 //   * frames that already live on the device skip the host stages (octvr_async_push_device): the mappers read
 //     the caller's device frames in place and one kernel (async_merge.hip) places the region frames into the
 //     caller's merged device frame; such frames travel the same queues, so pop order is push order;
-//   * the inputs may be packed UYVY 4:2:2 (OCTVR_PIX_UYVY422, what capture cards deliver): one plane per
-//     camera, the footprint runs of its packed rows copied and uploaded at 2 B per pixel, and one kernel
-//     (uyvy.hip) converts them into the slot's NV12 device frames — once for all mappers, which stay on NV12
-//     input; device frames are converted the same way from the caller's frames;
-//   * or any other 8-bit 4:2:2 capture layout (OCTVR_PIX_YUYV422, _YUV422P, _NV16; yuv422.hip): the same table
-//     and buffers, a run packed as its two luma rows and its two chroma rows (4 B per pixel of the run too).
-//   * or a 10-bit layout (OCTVR_PIX_P010, _YUV420P10, _P210, _YUV422P10; yuv10.hip): the same pieces with the
-//     format's own offsets (6 or 8 B per pixel of the run: yuv10_run_table), narrowed into the same NV12 frames.
+//   * the inputs may be in a converted capture layout (frame_layout.hpp: packed UYVY 4:2:2, what capture cards
+//     deliver, YUYV, YUV422P, NV16 and the 10-bit P010, YUV420P10, P210, YUV422P10): the footprint runs of the
+//     layout's planes copied and uploaded at the layout's 4, 6 or 8 B per pixel of a run's row (pack_run,
+//     run_table), and one kernel (frame_layout.hip) converts them into the slot's NV12 device frames — once for all
+//     mappers, which stay on NV12 input; device frames are converted the same way from the caller's frames.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -56,10 +53,8 @@
 
 #include "abi_guard.hpp"
 #include "async_host.hpp"
+#include "frame_layout.hpp"
 #include "mapper.hpp"
-#include "uyvy_host.hpp"
-#include "yuv422_host.hpp"
-#include "yuv10_host.hpp"
 
 using namespace octvr;
 
@@ -269,24 +264,17 @@ struct octvr_async {
     std::vector<FootRun> runs;  // what the mappers read of the inputs (footprint_runs)
     size_t packed_bytes = 0;
     DevBuf<FootRun> runs_dev;
-    // UYVY input: the unpack kernel's pieces over the same runs with their places in the packed buffers
-    // (uyvy_run_table), built when the format is first set
-    // (shared by the YUYV / YUV422P / NV16 inputs: every 4:2:2 layout packs a piece into the same 4 B per pixel)
-    // (the 10-bit layouts take the same pieces at 6 or 8 B per pixel: the table is rebuilt when uy_bpp changes)
-    bool in_422() const { return converted_format(in_fmt); }
+    // a converted input layout: the unpack kernel's pieces over the same runs with their places in the packed
+    // buffers (run_table), built when such a format is first set and again when conv_bpp changes
+    bool in_conv() const { return converted_format(in_fmt); }
     // the unpack launch of the input format over the table, from the packed buffer or the caller's frames
-    void unpack_422(const UyvySources& src, const FootFrames& frames, hipStream_t s) {
-        if (in_fmt == OCTVR_PIX_UYVY422)
-            HIP_CHECK(launch_uyvy_unpack(uy_table_dev.p, (int)uy_table.size(), src, frames, s));
-        else if (yuv10_format(in_fmt))
-            HIP_CHECK(launch_yuv10_unpack(in_fmt - kYuv10First, uy_table_dev.p, (int)uy_table.size(), src, frames, s));
-        else
-            HIP_CHECK(launch_yuv422_unpack(in_fmt - kYuv422First, uy_table_dev.p, (int)uy_table.size(), src, frames, s));
+    void conv_unpack(const ConvSources& src, const FootFrames& frames, hipStream_t s) {
+        HIP_CHECK(launch_layout_unpack(in_fmt, conv_table_dev.p, (int)conv_table.size(), src, frames, s));
     }
-    std::vector<UyvyRun> uy_table;
-    size_t uy_packed_bytes = 0;
-    int uy_bpp = 0;  // packed bytes per pixel of a piece's row the table's offsets were built with (0: no table)
-    DevBuf<UyvyRun> uy_table_dev;
+    std::vector<ConvRun> conv_table;
+    size_t conv_packed_bytes = 0;
+    int conv_bpp = 0;  // packed bytes per pixel of a piece's row the table's offsets were built with (0: no table)
+    DevBuf<ConvRun> conv_table_dev;
     Slot slots[kSlots];
     // output plane sets the caller registered (octvr_async_register_output): page-locked, downloaded into
     struct RegOut {
@@ -347,35 +335,14 @@ struct octvr_async {
         if (j.device) return;  // the mappers read the caller's frames in place
         stage(j, [&] {
             uint8_t* const dst = slots[s].packed_host->p;
-            if (in_fmt == OCTVR_PIX_UYVY422) {
-                copy_in_pool.run(uy_table.size(), [&](size_t lo, size_t hi) {
+            if (in_conv()) {
+                const LayoutDesc d = layout_of(in_fmt);
+                copy_in_pool.run(conv_table.size(), [&](size_t lo, size_t hi) {
                     for (size_t k = lo; k < hi; k++) {
-                        const UyvyRun& r = uy_table[k];
+                        const ConvRun& r = conv_table[k];
                         const int i = (int)(r.cam & 31u);
-                        uyvy_pack_run(dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng, j.in_planes[3 * i],
-                                      j.in_pitches[3 * i]);
-                    }
-                });
-                return;
-            }
-            if (yuv10_format(in_fmt)) {
-                copy_in_pool.run(uy_table.size(), [&](size_t lo, size_t hi) {
-                    for (size_t k = lo; k < hi; k++) {
-                        const UyvyRun& r = uy_table[k];
-                        const int i = (int)(r.cam & 31u);
-                        yuv10_pack_run(in_fmt - kYuv10First, dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng,
-                                       &j.in_planes[3 * i], &j.in_pitches[3 * i]);
-                    }
-                });
-                return;
-            }
-            if (yuv422_format(in_fmt)) {
-                copy_in_pool.run(uy_table.size(), [&](size_t lo, size_t hi) {
-                    for (size_t k = lo; k < hi; k++) {
-                        const UyvyRun& r = uy_table[k];
-                        const int i = (int)(r.cam & 31u);
-                        yuv422_pack_run(in_fmt - kYuv422First, dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng,
-                                        &j.in_planes[3 * i], &j.in_pitches[3 * i]);
+                        pack_run(d, dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng, &j.in_planes[3 * i],
+                                 &j.in_pitches[3 * i]);
                     }
                 });
                 return;
@@ -398,13 +365,13 @@ struct octvr_async {
         stage(j, [&] {
             DeviceGuard dg(device);
             Slot& sl = slots[j.slot];
-            if (in_422()) {
-                if (uy_packed_bytes) {
-                    HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, uy_packed_bytes, hipMemcpyHostToDevice, up));
-                    UyvySources src;
+            if (in_conv()) {
+                if (conv_packed_bytes) {
+                    HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, conv_packed_bytes, hipMemcpyHostToDevice, up));
+                    ConvSources src;
                     memset(&src, 0, sizeof src);
                     src.packed = sl.packed_dev.p;
-                    unpack_422(src, sl.frames, up);
+                    conv_unpack(src, sl.frames, up);
                 }
             } else if (packed_bytes) {
                 HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, packed_bytes, hipMemcpyHostToDevice, up));
@@ -422,21 +389,21 @@ struct octvr_async {
             Slot& sl = slots[j.slot];
             std::vector<const uint8_t*> in(n_in);
             std::vector<size_t> pitch(n_in);
-            // packed UYVY device frames are converted into the slot's frames first, once for all mappers
-            const bool own = !j.device || in_422();
+            // device frames of a converted layout are converted into the slot's frames first, once for all mappers
+            const bool own = !j.device || in_conv();
             for (int i = 0; i < n_in; i++) {
                 in[i] = own ? sl.in_dev[i].p : j.in_planes[i];
                 pitch[i] = own ? (size_t)in_w[i] : j.in_pitches[i];
             }
             if (j.device && j.ready) HIP_CHECK(hipStreamWaitEvent(comp, j.ready, 0));
-            if (j.device && in_422()) {
-                UyvySources src;
+            if (j.device && in_conv()) {
+                ConvSources src;
                 memset(&src, 0, sizeof src);
                 for (int i = 0; i < n_in; i++) {
                     src.f[i] = j.in_planes[i];
                     src.pitch[i] = j.in_pitches[i];
                 }
-                unpack_422(src, sl.frames, comp);
+                conv_unpack(src, sl.frames, comp);
             }
             // a device frame's single region covering the whole output is stitched where it belongs
             const bool in_place = j.device && whole_frame_region();
@@ -758,19 +725,15 @@ int octvr_async_push(octvr_async* a, const uint8_t* const* in_planes, const size
     for (int i = 0; i < a->n_in; i++) {
         const size_t w = (size_t)a->in_w[i];
         const int f = a->in_fmt;
-        // YUV422P's planes are the planar ones (Y, U, V; h chroma rows instead of h / 2): the last branch
-        // the 10-bit layouts: planes of 16-bit words (even addresses and pitches); P010 / P210 Y and a U,V plane of
-        // 2 w bytes a row, the planar two Y, U and V with w bytes a row of U and of V
-        auto even = [&](int k) { return yuv10_aligned(in_planes[3 * i + k], in_pitches[3 * i + k]); };
-        const bool bad = yuv10_format(f)
-                             ? (f == OCTVR_PIX_P010 || f == OCTVR_PIX_P210
-                                    ? !in_planes[3 * i] || !in_planes[3 * i + 1] || in_pitches[3 * i] < 2 * w ||
-                                          in_pitches[3 * i + 1] < 2 * w || !even(0) || !even(1)
-                                    : !in_planes[3 * i] || !in_planes[3 * i + 1] || !in_planes[3 * i + 2] ||
-                                          in_pitches[3 * i] < 2 * w || in_pitches[3 * i + 1] < w || in_pitches[3 * i + 2] < w ||
-                                          !even(0) || !even(1) || !even(2))
-                         : f == OCTVR_PIX_UYVY422 || f == OCTVR_PIX_YUYV422 ? !in_planes[3 * i] || in_pitches[3 * i] < 2 * w
-                         : f == OCTVR_PIX_NV12 || f == OCTVR_PIX_NV16
+        // a converted layout's planes (frame_layout.hpp pack_run): one packed plane; Y and a U,V plane; or Y, U
+        // and V with half a row's bytes each; planes of 16-bit words at even addresses and pitches
+        const LayoutDesc d = layout_of(f);
+        auto plane = [&](int k, size_t bytes) {
+            return in_planes[3 * i + k] && in_pitches[3 * i + k] >= bytes && d.aligned(in_planes[3 * i + k], in_pitches[3 * i + k]);
+        };
+        const size_t rb = (size_t)d.row_bytes((int)w);
+        const bool bad = d.converted() ? !(plane(0, rb) && (d.packed() || (d.halves() ? plane(1, rb / 2) && plane(2, rb / 2) : plane(1, rb))))
+                         : f == OCTVR_PIX_NV12
                              ? !in_planes[3 * i] || !in_planes[3 * i + 1] || in_pitches[3 * i] < w || in_pitches[3 * i + 1] < w
                              : !in_planes[3 * i] || !in_planes[3 * i + 1] || !in_planes[3 * i + 2] || in_pitches[3 * i] < w ||
                                    in_pitches[3 * i + 1] < w / 2 || in_pitches[3 * i + 2] < w / 2;
@@ -806,16 +769,11 @@ int octvr_async_push_device(octvr_async* a, const uint8_t* const* in_dev, const 
         for (int i = 0; i < a->n_in; i++) {
             REQUIRE(in_dev[i], "NULL input frame");
             // the limits mapper_stitch sets (mapper.cpp checked_source_frame), refused here before anything is queued
-            if (a->in_fmt == OCTVR_PIX_UYVY422) {  // a packed frame of in_h rows, converted by the pipeline
-                REQUIRE(in_pitch[i] >= (size_t)2 * (size_t)a->in_w[i], "UYVY input pitch smaller than two bytes per pixel");
-                REQUIRE((uint64_t)in_pitch[i] * (uint64_t)a->in_h[i] < 0x7FFFFFFFull, "input frame too large");
-                continue;
-            }
-            if (yuv10_format(a->in_fmt))
-                REQUIRE(yuv10_aligned(in_dev[i], in_pitch[i]), "10-bit input frames and pitches must be multiples of 2");
-            if (yuv422_format(a->in_fmt) || yuv10_format(a->in_fmt)) {  // a whole frame of the layout, converted by the pipeline
-                REQUIRE(in_pitch[i] >= frame422_row_bytes(a->in_fmt, a->in_w[i]), "4:2:2 input pitch smaller than a row of the format");
-                REQUIRE((uint64_t)in_pitch[i] * (uint64_t)frame422_rows(a->in_fmt, a->in_h[i]) < 0x7FFFFFFFull, "input frame too large");
+            if (a->in_conv()) {  // a whole frame of the layout, converted by the pipeline
+                const LayoutDesc d = layout_of(a->in_fmt);
+                REQUIRE(d.aligned(in_dev[i], in_pitch[i]), "10-bit input frames and pitches must be multiples of 2");
+                REQUIRE(in_pitch[i] >= (size_t)d.row_bytes(a->in_w[i]), "input pitch smaller than a row of the format");
+                REQUIRE((uint64_t)in_pitch[i] * (uint64_t)d.rows(a->in_h[i]) < 0x7FFFFFFFull, "input frame too large");
                 continue;
             }
             REQUIRE(in_pitch[i] >= (size_t)a->in_w[i], "input pitch smaller than width");
@@ -942,20 +900,11 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
             return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || converted_format(f);
         };
         REQUIRE(known(in_format) && known(out_format), "pixel format must be an OCTVR_PIX_* value");
-        if (yuv10_format(out_format))
+        if (converted_format(out_format))
             throw OctvrError(OCTVR_E_UNSUPPORTED,
-                             "the 10-bit layouts are input formats of the pipeline only: its merge, copy-out and registered "
-                             "output planes are per-plane tables of an 8-bit 4:2:0 frame (a Mapper writes them: "
+                             "the converted layouts (4:2:2, 10-bit) are input formats of the pipeline only: its merge, copy-out "
+                             "and registered output planes are per-plane tables of an 8-bit 4:2:0 frame (a Mapper writes them: "
                              "octvr_mapper_set_pixel_formats)");
-        if (yuv422_format(out_format))
-            throw OctvrError(OCTVR_E_UNSUPPORTED,
-                             "the 4:2:2 layouts are input formats of the pipeline only: its merge, copy-out and registered "
-                             "output planes are per-plane tables of a 4:2:0 frame (a Mapper writes them: "
-                             "octvr_mapper_set_pixel_formats)");
-        if (out_format == OCTVR_PIX_UYVY422)
-            throw OctvrError(OCTVR_E_UNSUPPORTED,
-                             "UYVY is an input format of the pipeline only: its merge, copy-out and registered output "
-                             "planes are per-plane tables (a Mapper writes UYVY: octvr_mapper_set_pixel_formats)");
         REQUIRE(a->pending == 0, "frames pending: pop them before changing the pixel formats");
         REQUIRE(out_format == a->out_fmt || a->reg_out.empty(),
                 "output planes are registered: unregister them before changing the output format");
@@ -963,28 +912,27 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
         // U and V rows together, which needs even widths (they are, since creation)
         for (int w : a->in_w) REQUIRE(w % 2 == 0, "input widths must be even");
         DeviceGuard dg0(a->device);
-        const bool in422 = converted_format(in_format);
-        // the pieces' places in the packed buffer are the format's own: 4 bytes per pixel of a piece's row for the
-        // 8-bit 4:2:2 layouts, 6 or 8 for the 10-bit ones; a switch between them rebuilds the table
-        const int bpp = yuv10_format(in_format) ? yuv10_run_bpp(in_format - kYuv10First) : 4;
-        if (in422 && a->uy_bpp != bpp && !a->runs.empty()) {
+        const LayoutDesc in_layout = layout_of(in_format);
+        const bool in_conv = in_layout.converted();
+        // the pieces' places in the packed buffer are the format's own: 4, 6 or 8 bytes per pixel of a piece's row;
+        // a switch between them rebuilds the table
+        if (in_conv && a->conv_bpp != in_layout.run_bpp() && !a->runs.empty()) {
             size_t bytes = 0;
-            std::vector<UyvyRun> t = yuv10_format(in_format) ? yuv10_run_table(in_format - kYuv10First, a->runs, a->in_w, bytes)
-                                                             : uyvy_run_table(a->runs, a->in_w, bytes);
+            std::vector<ConvRun> t = run_table(in_layout, a->runs, a->in_w, bytes);
             REQUIRE(bytes < ((size_t)1 << 32) && t.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
-            a->uy_table_dev.upload(t.data(), t.size());
-            for (auto& sl : a->slots)  // 4 bytes per pixel pair row against 3: larger packed buffers
+            a->conv_table_dev.upload(t.data(), t.size());
+            for (auto& sl : a->slots)  // 4 to 8 bytes per pixel of a row pair against 3: larger packed buffers
                 if (sl.packed_host->n < bytes) {
                     sl.packed_host.reset(new PinnedBuf());
                     sl.packed_host->alloc(bytes);
                     sl.packed_dev.alloc(bytes);
                 }
-            a->uy_table = std::move(t);
-            a->uy_packed_bytes = bytes;
-            a->uy_bpp = bpp;
+            a->conv_table = std::move(t);
+            a->conv_packed_bytes = bytes;
+            a->conv_bpp = in_layout.run_bpp();
         }
-        // a 4:2:2 pipeline converts once for all its mappers, which read its NV12 frames
-        const int mapper_in = in422 ? OCTVR_PIX_NV12 : in_format;
+        // a pipeline with a converted input converts once for all its mappers, which read its NV12 frames
+        const int mapper_in = in_conv ? OCTVR_PIX_NV12 : in_format;
         for (octvr_mapper* m : a->mappers) {
             const int rc = octvr_mapper_set_pixel_formats(m, mapper_in, out_format);
             if (rc != OCTVR_OK) throw OctvrError(rc, octvr_last_error());

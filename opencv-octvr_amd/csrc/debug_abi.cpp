@@ -26,24 +26,16 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
         REQUIRE(n_inputs > 0 && n_inputs <= kMaxCams && n_runs >= 0, "bad counts");
         REQUIRE(format == OCTVR_PIX_YUV420P || format == OCTVR_PIX_NV12 || converted_format(format),
                 "pixel format must be an OCTVR_PIX_* value");
-        const bool nv12 = format == OCTVR_PIX_NV12, uyvy = format == OCTVR_PIX_UYVY422, y422 = yuv422_format(format);
-        const bool y10 = yuv10_format(format);
+        const bool nv12 = format == OCTVR_PIX_NV12;
+        const LayoutDesc d = layout_of(format);
         for (int i = 0; i < n_inputs; i++) {
             const size_t w = (size_t)in_w[i];
             REQUIRE(in_w[i] > 0 && in_h[i] > 0 && in_w[i] % 2 == 0 && in_h[i] % 2 == 0, "input sizes must be even");
-            if (y10) {  // planes of 16-bit words: Y and U,V pairs of 2 w bytes per row, or Y, U and V (w bytes per row)
-                const bool semi = format == OCTVR_PIX_P010 || format == OCTVR_PIX_P210;
-                REQUIRE(planes[3 * i] && planes[3 * i + 1] && pitches[3 * i] >= 2 * w && pitches[3 * i + 1] >= (semi ? 2 * w : w),
+            if (d.converted()) {  // one packed plane; Y and a U,V plane; or Y, U and V with half a row's bytes each
+                const size_t rb = (size_t)d.row_bytes(in_w[i]);
+                auto plane = [&](int k, size_t bytes) { return planes[3 * i + k] && pitches[3 * i + k] >= bytes; };
+                REQUIRE(plane(0, rb) && (d.packed() || (d.halves() ? plane(1, rb / 2) && plane(2, rb / 2) : plane(1, rb))),
                         "bad input plane");
-                REQUIRE(semi || (planes[3 * i + 2] && pitches[3 * i + 2] >= w), "bad input plane");
-                continue;
-            }
-            if (uyvy || format == OCTVR_PIX_YUYV422) {  // one packed plane of 2 w bytes per row
-                REQUIRE(planes[3 * i] && pitches[3 * i] >= 2 * w, "bad input plane");
-                continue;
-            }
-            if (format == OCTVR_PIX_NV16) {  // Y and a U,V plane of w bytes per row
-                REQUIRE(planes[3 * i] && planes[3 * i + 1] && pitches[3 * i] >= w && pitches[3 * i + 1] >= w, "bad input plane");
                 continue;
             }
             REQUIRE(planes[3 * i] && planes[3 * i + 1] && pitches[3 * i] >= w, "bad input plane");
@@ -59,14 +51,11 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
             const int w = in_w[cam], h = in_h[cam];
             REQUIRE(rp < (uint32_t)h / 2 && ng > 0 && g0 < (uint32_t)(w + 7) / 8 && ng <= (uint32_t)(w + 7) / 8 - g0,
                     "run outside its frame");
-            const size_t n = (y10 ? yuv10_run_bpp(format - kYuv10First) : uyvy || y422 ? 4 : 3) * (size_t)run_luma_bytes(w, (int)g0, (int)ng);
+            const size_t n = (size_t)(d.converted() ? d.run_bpp() : 3) * (size_t)run_luma_bytes(w, (int)g0, (int)ng);
             REQUIRE(off + n <= cap, "buffer too small");
-            const size_t got = y10    ? yuv10_pack_run(format - kYuv10First, packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam,
-                                                       pitches + 3 * cam)
-                               : uyvy ? uyvy_pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes[3 * cam], pitches[3 * cam])
-                               : y422 ? yuv422_pack_run(format - kYuv422First, packed + off, w, (int)rp, (int)g0, (int)ng,
-                                                        planes + 3 * cam, pitches + 3 * cam)
-                                      : pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam, nv12);
+            const size_t got = d.converted()
+                                   ? pack_run(d, packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam)
+                                   : pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam, nv12);
             REQUIRE(got == n, "pack_run size");
             if (sizes) sizes[k] = got;
             off += got;
@@ -78,12 +67,12 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
 int octvr_debug_mapper_uyvy_runs(const octvr_mapper* m, uint32_t* runs, size_t cap, size_t* count) {
     return guarded([&] {
         REQUIRE(m && count, "NULL argument");
-        REQUIRE(m->uy_in && m->fmt422_in == OCTVR_PIX_UYVY422, "the mapper's input format is not OCTVR_PIX_UYVY422");
-        *count = m->uy_foot_runs.size();
+        REQUIRE(m->conv_in && m->conv_fmt_in == OCTVR_PIX_UYVY422, "the mapper's input format is not OCTVR_PIX_UYVY422");
+        *count = m->conv_foot_runs.size();
         if (!runs) return;
-        REQUIRE(cap >= m->uy_foot_runs.size(), "buffer too small");
-        for (size_t k = 0; k < m->uy_foot_runs.size(); k++) {
-            const FootRun& r = m->uy_foot_runs[k];
+        REQUIRE(cap >= m->conv_foot_runs.size(), "buffer too small");
+        for (size_t k = 0; k < m->conv_foot_runs.size(); k++) {
+            const FootRun& r = m->conv_foot_runs[k];
             runs[4 * k] = r.cam & 31u;
             runs[4 * k + 1] = r.cam >> 8;
             runs[4 * k + 2] = r.g0;

@@ -293,35 +293,24 @@ hipError_t launch_unpack_runs_layout(const uint8_t* packed, const FootRun* runs,
 // build_merge_table) into its place in the merged device frame `out`, one launch.
 struct MergeTable;
 hipError_t launch_merge_regions(uint8_t* out, const MergeTable& t, hipStream_t s);
-// Packed UYVY 4:2:2 frames (OCTVR_PIX_UYVY422, uyvy.hip; the arithmetic and the table in uyvy_host.hpp).
-// launch_uyvy_unpack: the groups of the table's pieces from packed 4:2:2 sources into the cameras' NV12 frames
-// `frames` (pitch = width).  The sources are the pipeline's packed upload buffer (`packed`, each piece at its
-// `off`) or, with packed NULL, one frame per camera at its pitch (>= 2 w).
-struct UyvyRun;
-struct UyvySources {
+// The converted capture layouts (the OCTVR_PIX_* values >= 16, frame_layout.hip; the arithmetic, the table and the
+// layouts' descriptors in frame_layout.hpp; `pix` is the OCTVR_PIX_* value).
+// launch_layout_unpack: the groups of the table's pieces from sources of the layout into the cameras' NV12 frames
+// `frames` (pitch = width).  The sources are the pipeline's packed upload buffer (`packed`, pack_run's pieces, each
+// at its `off` of run_table) or, with packed NULL, one whole frame of the layout per camera at its pitch (>= the
+// layout's row bytes; base and pitch even for 16-bit samples).
+struct ConvRun;
+struct ConvSources {
     const uint8_t* packed;
     const uint8_t* f[kMaxCams];
     size_t pitch[kMaxCams];
 };
-hipError_t launch_uyvy_unpack(const UyvyRun* table, int n_pieces, const UyvySources& src, const FootFrames& frames,
-                              hipStream_t s);
-// launch_uyvy_pack: the whole w x h NV12 frame `src` (pitch = w) into the packed frame `out` at `pitch` (>= 2 w,
-// any alignment); bytes of a row past 2 w are not written.
-hipError_t launch_uyvy_pack(const uint8_t* src, int w, int h, uint8_t* out, size_t pitch, hipStream_t s);
-// The other 8-bit 4:2:2 layouts (OCTVR_PIX_YUYV422 / YUV422P / NV16, yuv422.hip; `layout` is yuv422_host.hpp's
-// Yuv422Layout): the same table, sources and NV12 frames as the UYVY launches.  A frame source is the caller's
-// whole frame in the layout (YUYV: pitch >= 2 w; the planar ones: 2 h rows, pitch >= w), the packed buffer holds
-// yuv422_pack_run's pieces.  The pack writes no byte of a row past its width.
-hipError_t launch_yuv422_unpack(int layout, const UyvyRun* table, int n_pieces, const UyvySources& src,
-                                const FootFrames& frames, hipStream_t s);
-hipError_t launch_yuv422_pack(int layout, const uint8_t* src, int w, int h, uint8_t* out, size_t pitch, hipStream_t s);
-// The 10-bit layouts (OCTVR_PIX_P010 / YUV420P10 / P210 / YUV422P10, yuv10.hip; `layout` is yuv10_host.hpp's
-// Yuv10Layout): the same table pieces, sources and 8-bit NV12 frames.  A frame source is the caller's whole frame
-// of 16-bit words (3 h / 2 or 2 h rows, pitch >= 2 w, base and pitch even), the packed buffer holds
-// yuv10_pack_run's pieces at the offsets of yuv10_run_table.  The pack writes no byte of a row past 2 w.
-hipError_t launch_yuv10_unpack(int layout, const UyvyRun* table, int n_pieces, const UyvySources& src,
-                               const FootFrames& frames, hipStream_t s);
-hipError_t launch_yuv10_pack(int layout, const uint8_t* src, int w, int h, uint8_t* out, size_t pitch, hipStream_t s);
+hipError_t launch_layout_unpack(int pix, const ConvRun* table, int n_pieces, const ConvSources& src, const FootFrames& frames,
+                                hipStream_t s);
+// launch_layout_pack: the whole w x h NV12 frame `src` (pitch = w) into the frame `out` of the layout at `pitch`
+// (>= the layout's row bytes, any alignment; even base and pitch for 16-bit samples); bytes of a row past the
+// layout's row bytes are not written.
+hipError_t launch_layout_pack(int pix, const uint8_t* src, int w, int h, uint8_t* out, size_t pitch, hipStream_t s);
 
 struct TiledLut {
     const TileHdr* meta;          // per staged item kMetaWords 16-byte words: the TileHdr, then kTileSlots TileSlots

@@ -85,15 +85,11 @@ void setup_overlays(octvr_mapper& m, const Camera& camera) {
 }
 
 void check_out_pitch(const octvr_mapper* m, size_t out_pitch) {
-    if (m->uy_out && m->fmt422_out == OCTVR_PIX_UYVY422) {  // a packed frame of SH rows; the stitch writes the slot's own 4:2:0 frame
-        REQUIRE(out_pitch >= (size_t)2 * (size_t)m->SW, "UYVY output pitch smaller than two bytes per pixel");
-        REQUIRE((uint64_t)out_pitch * (uint64_t)m->SH < 0x7FFFFF80ull, "output frame larger than 2 GiB");
-        return;
-    }
-    if (m->uy_out) {  // YUYV: SH rows of 2 SW bytes; YUV422P and NV16: 2 SH rows of SW bytes; 10-bit: rows of 2 SW bytes
-        REQUIRE(out_pitch >= frame422_row_bytes(m->fmt422_out, m->SW), "4:2:2 output pitch smaller than a row of the format");
-        REQUIRE(!yuv10_format(m->fmt422_out) || (out_pitch & 1) == 0, "10-bit output pitch must be a multiple of 2");
-        REQUIRE((uint64_t)out_pitch * (uint64_t)frame422_rows(m->fmt422_out, m->SH) < 0x7FFFFF80ull, "output frame larger than 2 GiB");
+    if (m->conv_out) {  // a whole frame of the layout; the stitch writes the slot's own NV12 frame
+        const LayoutDesc d = layout_of(m->conv_fmt_out);
+        REQUIRE(out_pitch >= (size_t)d.row_bytes(m->SW), "output pitch smaller than a row of the format");
+        REQUIRE(d.aligned(nullptr, out_pitch), "10-bit output pitch must be a multiple of 2");
+        REQUIRE((uint64_t)out_pitch * (uint64_t)d.rows(m->SH) < 0x7FFFFF80ull, "output frame larger than 2 GiB");
         return;
     }
     REQUIRE(out_pitch >= (size_t)m->SW, "output pitch smaller than width");
@@ -109,77 +105,61 @@ FrameSet frame_set(const octvr_mapper* m, const uint8_t* const* in_dev, const si
     return fs;
 }
 
-// The packed frames of a UYVY stitch, checked before anything is put on the stream.
-UyvySources uyvy_sources(const octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch) {
-    UyvySources us;
-    memset(&us, 0, sizeof us);
+// The caller's frames of a converted input side, checked before anything is put on the stream.
+ConvSources conv_sources(const octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch) {
+    ConvSources cs;
+    memset(&cs, 0, sizeof cs);
+    const LayoutDesc d = layout_of(m->conv_fmt_in);
     for (int i = 0; i < m->nc; i++) {
         REQUIRE(in_dev[i], "bad input frame");
-        if (m->fmt422_in == OCTVR_PIX_UYVY422) {
-            REQUIRE(in_pitch[i] >= (size_t)2 * (size_t)m->in_w[i], "UYVY input pitch smaller than two bytes per pixel");
-            REQUIRE((uint64_t)in_pitch[i] * (uint64_t)m->in_h[i] < 0x7FFFFFFFull, "input frame larger than 2 GiB");
-        } else {
-            REQUIRE(in_pitch[i] >= frame422_row_bytes(m->fmt422_in, m->in_w[i]), "4:2:2 input pitch smaller than a row of the format");
-            REQUIRE(!yuv10_format(m->fmt422_in) || yuv10_aligned(in_dev[i], in_pitch[i]),
-                    "10-bit input frames and pitches must be multiples of 2");
-            REQUIRE((uint64_t)in_pitch[i] * (uint64_t)frame422_rows(m->fmt422_in, m->in_h[i]) < 0x7FFFFFFFull,
-                    "input frame larger than 2 GiB");
-        }
-        us.f[i] = in_dev[i];
-        us.pitch[i] = in_pitch[i];
+        REQUIRE(in_pitch[i] >= (size_t)d.row_bytes(m->in_w[i]), "input pitch smaller than a row of the format");
+        REQUIRE(d.aligned(in_dev[i], in_pitch[i]), "10-bit input frames and pitches must be multiples of 2");
+        REQUIRE((uint64_t)in_pitch[i] * (uint64_t)d.rows(m->in_h[i]) < 0x7FFFFFFFull, "input frame larger than 2 GiB");
+        cs.f[i] = in_dev[i];
+        cs.pitch[i] = in_pitch[i];
     }
-    return us;
+    return cs;
 }
 
-// The slot's unpack launch over the mapper's footprint, and the 4:2:0 frames every later stage reads.
-// The pack launch of a 4:2:2 output side: the slot's NV12 output frame into the caller's frame.
-void pack_422(const octvr_mapper* m, const uint8_t* src, uint8_t* out, size_t pitch, hipStream_t s) {
-    if (m->fmt422_out == OCTVR_PIX_UYVY422)
-        HIP_CHECK(launch_uyvy_pack(src, m->SW, m->SH, out, pitch, s));
-    else if (yuv10_format(m->fmt422_out))
-        HIP_CHECK(launch_yuv10_pack(m->fmt422_out - kYuv10First, src, m->SW, m->SH, out, pitch, s));
-    else
-        HIP_CHECK(launch_yuv422_pack(m->fmt422_out - kYuv422First, src, m->SW, m->SH, out, pitch, s));
+// The pack launch of a converted output side: the slot's NV12 output frame into the caller's frame.
+void conv_pack(const octvr_mapper* m, const uint8_t* src, uint8_t* out, size_t pitch, hipStream_t s) {
+    HIP_CHECK(launch_layout_pack(m->conv_fmt_out, src, m->SW, m->SH, out, pitch, s));
 }
 
-FrameSet uyvy_unpack_slot(const octvr_mapper* m, const octvr_mapper::FrameSlot& sl, const UyvySources& us, hipStream_t s) {
-    if (m->fmt422_in == OCTVR_PIX_UYVY422)
-        HIP_CHECK(launch_uyvy_unpack(m->uy_table.p, (int)m->uy_table.n, us, *sl.uy_in, s));
-    else if (yuv10_format(m->fmt422_in))  // the table's offsets are not read: the sources are frames
-        HIP_CHECK(launch_yuv10_unpack(m->fmt422_in - kYuv10First, m->uy_table.p, (int)m->uy_table.n, us, *sl.uy_in, s));
-    else
-        HIP_CHECK(launch_yuv422_unpack(m->fmt422_in - kYuv422First, m->uy_table.p, (int)m->uy_table.n, us, *sl.uy_in, s));
+// The slot's unpack launch over the mapper's footprint, and the NV12 frames every later stage reads.
+FrameSet conv_unpack_slot(const octvr_mapper* m, const octvr_mapper::FrameSlot& sl, const ConvSources& cs, hipStream_t s) {
+    HIP_CHECK(launch_layout_unpack(m->conv_fmt_in, m->conv_table.p, (int)m->conv_table.n, cs, *sl.conv_in, s));
     FrameSet fs;
     memset(&fs, 0, sizeof fs);
     for (int i = 0; i < m->nc; i++)
-        fs.f[i] = checked_source_frame(sl.uy_in->f[i], (size_t)m->in_w[i], m->in_w[i], m->in_h[i], m->vig[i].p);
+        fs.f[i] = checked_source_frame(sl.conv_in->f[i], (size_t)m->in_w[i], m->in_w[i], m->in_h[i], m->vig[i].p);
     return fs;
 }
 
 // ---- frame slots -------------------------------------------------------------------------------------
-// The slot's 4:2:0 frames of the packed UYVY sides, as the mapper's formats say (allocated or freed).  The
+// The slot's NV12 frames of the converted sides, as the mapper's formats say (allocated or freed).  The
 // input frames hold the fixed pattern of the AsyncMultiMapper's slots outside the footprint: nothing reads it.
-void slot_uyvy(const octvr_mapper& m, octvr_mapper::SlotBufs& b, octvr_mapper::FrameSlot& sl) {
-    b.uy_in.clear();
-    b.uy_frames = FootFrames{};
-    b.uy_out.reset();
-    sl.uy_in = nullptr;
-    sl.uy_out = nullptr;
-    if (m.uy_in) {
-        b.uy_in.resize(m.nc);
+void slot_conv(const octvr_mapper& m, octvr_mapper::SlotBufs& b, octvr_mapper::FrameSlot& sl) {
+    b.conv_in.clear();
+    b.conv_frames = FootFrames{};
+    b.conv_out.reset();
+    sl.conv_in = nullptr;
+    sl.conv_out = nullptr;
+    if (m.conv_in) {
+        b.conv_in.resize(m.nc);
         for (int i = 0; i < m.nc; i++) {
             const size_t bytes = (size_t)m.in_w[i] * (size_t)(m.in_h[i] / 2 * 3);
-            b.uy_in[i].alloc(bytes);
-            HIP_CHECK(hipMemset(b.uy_in[i].p, 0x5A, bytes));
-            b.uy_frames.f[i] = b.uy_in[i].p;
-            b.uy_frames.w[i] = m.in_w[i];
-            b.uy_frames.h[i] = m.in_h[i];
+            b.conv_in[i].alloc(bytes);
+            HIP_CHECK(hipMemset(b.conv_in[i].p, 0x5A, bytes));
+            b.conv_frames.f[i] = b.conv_in[i].p;
+            b.conv_frames.w[i] = m.in_w[i];
+            b.conv_frames.h[i] = m.in_h[i];
         }
-        sl.uy_in = &b.uy_frames;
+        sl.conv_in = &b.conv_frames;
     }
-    if (m.uy_out) {
-        b.uy_out.alloc((size_t)m.SW * (size_t)(m.SH / 2 * 3));
-        sl.uy_out = b.uy_out.p;
+    if (m.conv_out) {
+        b.conv_out.alloc((size_t)m.SW * (size_t)(m.SH / 2 * 3));
+        sl.conv_out = b.conv_out.p;
     }
 }
 
@@ -204,7 +184,7 @@ octvr_mapper::FrameSlot make_slot(octvr_mapper& m) {
     sl.totals = b->totals.p;
     sl.tickets = b->tickets.p;
     sl.queue = b->queue.p;
-    slot_uyvy(m, *b, sl);
+    slot_conv(m, *b, sl);
     m.slot_bufs.push_back(std::move(b));
     return sl;
 }
@@ -296,7 +276,7 @@ struct TimedPair {
 // (a few more bytes for fewer, longer copies: the AsyncMultiMapper's host copies bridge kRunGap).  A cell (row
 // pair r, group g) is the same pixels in every input layout, and with an even width a run's NV12 chroma row (yb
 // bytes at byte 8 g0) is as long as its planar U and V rows together (2 cb): offsets and sizes hold for both
-// 4:2:0 layouts (a packed UYVY source has its own offsets, uyvy_run_table).
+// 4:2:0 layouts (a converted layout has its own offsets, frame_layout.hpp run_table).
 std::vector<FootRun> footprint_runs(const SourceFootprint& f, size_t& bytes, int gap) {
     std::vector<FootRun> runs;
     bytes = 0;
@@ -325,17 +305,17 @@ std::vector<FootRun> footprint_runs(const SourceFootprint& f, size_t& bytes, int
     return runs;
 }
 
-// The stitch of a UYVY side runs on NV12 frames of the frame slot: NV12 because a packed group's chroma is
-// already U,V pairs (one 8-byte chroma store per group in, one 8-byte chroma load per chunk out, no split into
-// a U and a V half), and because UYVY in and out then take the composite's compiled-in NV12 instance.
-// The other 4:2:2 layouts take the same frames, table and runs; only the two launches differ (pack_422).
-void mapper_set_uyvy(octvr_mapper* m, int in_fmt, int out_fmt) {
+// The stitch of a converted side runs on NV12 frames of the frame slot: NV12 because a packed or U,V group's
+// chroma is already U,V pairs (one 8-byte chroma store per group in, one 8-byte chroma load per chunk out, no
+// split into a U and a V half), and because every layout in and out then takes the composite's compiled-in NV12
+// instance.  The layouts share the frames, the table and the runs; only the two launches' format differs.
+void mapper_set_conv(octvr_mapper* m, int in_fmt, int out_fmt) {
     const bool in = in_fmt != 0, out = out_fmt != 0;
-    m->fmt422_in = in_fmt;  // the slot frames depend on the sides being 4:2:2 only, not on the layout
-    m->fmt422_out = out_fmt;
-    if (in == m->uy_in && out == m->uy_out) return;
+    m->conv_fmt_in = in_fmt;  // the slot frames depend on the sides being converted only, not on the layout
+    m->conv_fmt_out = out_fmt;
+    if (in == m->conv_in && out == m->conv_out) return;
     DeviceGuard dg(m->device);
-    if (in && !m->uy_table.p) {
+    if (in && !m->conv_table.p) {
         // every source read of the mapper lies in its footprint (host_common.hpp SourceFootprint: the staged
         // groups, the wide tiles', the multi-band remap's, the overlays' and the gain samples' taps, in either
         // sampling convention; the gathered preview's taps are the composite's) — what the AsyncMultiMapper's
@@ -343,15 +323,18 @@ void mapper_set_uyvy(octvr_mapper* m, int in_fmt, int out_fmt) {
         size_t bytes420 = 0;
         // no gaps bridged: a lane converts one group, a bridged group would only be more bytes
         const std::vector<FootRun> runs = footprint_runs(m->foot, bytes420, 0);
-        m->uy_foot_runs = runs;
-        const std::vector<UyvyRun> table = uyvy_run_table(runs, m->in_w, m->uy_in_bytes);
-        REQUIRE(m->uy_in_bytes < ((size_t)1 << 32) && table.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
-        m->uy_runs = runs.size();
-        m->uy_table.upload(table.data(), table.size());
+        m->conv_foot_runs = runs;
+        // the pieces are the same in every layout; the offsets (4 bytes per pixel here) are not read
+        size_t bytes4 = 0;
+        const std::vector<ConvRun> table = run_table(LayoutUyvy::desc, runs, m->in_w, bytes4);
+        REQUIRE(bytes4 < ((size_t)1 << 32) && table.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
+        m->conv_in_px = bytes4 / 4;
+        m->conv_runs = runs.size();
+        m->conv_table.upload(table.data(), table.size());
     }
-    m->uy_in = in;
-    m->uy_out = out;
-    for (size_t k = 0; k < m->slots.size(); k++) slot_uyvy(*m, *m->slot_bufs[k], m->slots[k]);
+    m->conv_in = in;
+    m->conv_out = out;
+    for (size_t k = 0; k < m->slots.size(); k++) slot_conv(*m, *m->slot_bufs[k], m->slots[k]);
     HIP_CHECK(hipDeviceSynchronize());  // the memsets complete before any stream uses the frames
 }
 
@@ -374,14 +357,14 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
         }
     }
     check_out_pitch(m, out_pitch);
-    REQUIRE(!(m->uy_out && yuv10_format(m->fmt422_out)) || yuv10_aligned(out_dev, 0), "10-bit output frame must be 2-byte aligned");
+    REQUIRE(!m->conv_out || layout_of(m->conv_fmt_out).aligned(out_dev, 0), "10-bit output frame must be 2-byte aligned");
     DeviceGuard dg(m->device);
-    // packed UYVY sides: the slot's unpack launch fills its 4:2:0 input frames, which every stage below reads,
-    // and the stitch writes the slot's 4:2:0 output frame, which the pack launch converts at the end
-    UyvySources us;
+    // converted sides: the slot's unpack launch fills its NV12 input frames, which every stage below reads,
+    // and the stitch writes the slot's NV12 output frame, which the pack launch converts at the end
+    ConvSources us;
     FrameSet fs;
-    if (m->uy_in)
-        us = uyvy_sources(m, in_dev, in_pitch);
+    if (m->conv_in)
+        us = conv_sources(m, in_dev, in_pitch);
     else
         fs = frame_set(m, in_dev, in_pitch);
     REQUIRE(!m->use_gain || gains_dev || !gains || n_gains == m->n, "gains must have one entry per input");
@@ -390,21 +373,21 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
     hipEvent_t e0 = ev.e0, e1 = ev.e1;
     const bool timed = e0 != nullptr;
     // the events bracket the conversions too
-    const bool outer = m->scaled || m->mb || preview || m->uy_in || m->uy_out;
-    if (m->uy_in) {
+    const bool outer = m->scaled || m->mb || preview || m->conv_in || m->conv_out;
+    if (m->conv_in) {
         if (timed) HIP_CHECK(hipEventRecord(e0, s));
-        fs = uyvy_unpack_slot(m, sl, us, s);
+        fs = conv_unpack_slot(m, sl, us, s);
     }
     stitch_gains(m, sl, fs, gains, gains_dev, s);
     uint8_t* const caller_out = out_dev;
     const size_t caller_pitch = out_pitch;
-    if (m->uy_out) {
-        out_dev = sl.uy_out;
+    if (m->conv_out) {
+        out_dev = sl.conv_out;
         out_pitch = (size_t)m->SW;
     }
     // overlays after a blend are copied onto the RGB(A) result too (mapper.cpp:279-287)
     const bool overlays = m->ov.view.n_groups > 0;
-    if (timed && outer && !m->uy_in) HIP_CHECK(hipEventRecord(e0, s));  // else the composite records its own
+    if (timed && outer && !m->conv_in) HIP_CHECK(hipEventRecord(e0, s));  // else the composite records its own
     if (m->scaled || (preview && !gathered) || overlays) {
         // stitch at template size into the RGB(A) result, then resize + RGB -> YUV420P (mapper.cpp:290-306)
         // (one frame slot only: the result frame is shared); without scaling the resize is the identity
@@ -431,7 +414,7 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
             HIP_CHECK(launch_preview_gather(fs, m->pv.view, sl.gains, m->use_gain, preview->dev, (int64_t)preview->pitch, s,
                                             m->pix));
     }
-    if (m->uy_out) pack_422(m, sl.uy_out, caller_out, caller_pitch, s);
+    if (m->conv_out) conv_pack(m, sl.conv_out, caller_out, caller_pitch, s);
     if (timed && outer) HIP_CHECK(hipEventRecord(e1, s));
     ev.keep();
     finish_slot(sl, s);
@@ -456,13 +439,13 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
     REQUIRE(nb <= 2 || m->nc <= 16, "a batch of 4 frames holds 16 cameras per frame (inputs and overlays)");
     check_out_pitch(m, out_pitch);
     for (int f = 0; f < nb; f++)
-        REQUIRE(!(m->uy_out && yuv10_format(m->fmt422_out)) || yuv10_aligned(out_dev[f], 0), "10-bit output frame must be 2-byte aligned");
+        REQUIRE(!m->conv_out || layout_of(m->conv_fmt_out).aligned(out_dev[f], 0), "10-bit output frame must be 2-byte aligned");
     DeviceGuard dg(m->device);
     FrameSet fs[kMaxBatch];  // every frame checked before any of them puts work on the stream
-    UyvySources us[kMaxBatch];
+    ConvSources us[kMaxBatch];
     for (int f = 0; f < nb; f++) {
-        if (m->uy_in)
-            us[f] = uyvy_sources(m, in_dev + (size_t)f * m->nc, in_pitch + (size_t)f * m->nc);
+        if (m->conv_in)
+            us[f] = conv_sources(m, in_dev + (size_t)f * m->nc, in_pitch + (size_t)f * m->nc);
         else
             fs[f] = frame_set(m, in_dev + (size_t)f * m->nc, in_pitch + (size_t)f * m->nc);
     }
@@ -473,13 +456,13 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
     uint32_t* tick[kMaxBatch];
     double* gd[kMaxBatch];
     TimedPair ev(m);
-    const bool outer = ev.e0 && (m->uy_in || m->uy_out);  // the events bracket the conversions too
+    const bool outer = ev.e0 && (m->conv_in || m->conv_out);  // the events bracket the conversions too
     uint8_t* out[kMaxBatch];
     for (int f = 0; f < nb; f++) {
         sl[f] = &take_slot(m, s);
         if (f == 0 && outer) HIP_CHECK(hipEventRecord(ev.e0, s));
-        if (m->uy_in) fs[f] = uyvy_unpack_slot(m, *sl[f], us[f], s);  // each frame converted in its own slot
-        out[f] = m->uy_out ? sl[f]->uy_out : out_dev[f];
+        if (m->conv_in) fs[f] = conv_unpack_slot(m, *sl[f], us[f], s);  // each frame converted in its own slot
+        out[f] = m->conv_out ? sl[f]->conv_out : out_dev[f];
         if (!feed) stitch_gains(m, *sl[f], fs[f], gains ? gains + (size_t)f * m->n : nullptr, nullptr, s);
         g[f] = sl[f]->gains;
         tot[f] = sl[f]->totals;
@@ -491,9 +474,9 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
                                          gd, s, true, m->pix));
     TiledLut view = m->tiles.view;
     view.queue = sl[0]->queue;  // this launch's work counters (the first frame's slot)
-    HIP_CHECK(launch_stitch_batch(fs, nb, view, m->W, m->H, g, m->use_gain, out, (int64_t)(m->uy_out ? (size_t)m->SW : out_pitch),
+    HIP_CHECK(launch_stitch_batch(fs, nb, view, m->W, m->H, g, m->use_gain, out, (int64_t)(m->conv_out ? (size_t)m->SW : out_pitch),
                                   s, outer ? nullptr : ev.e0, outer ? nullptr : ev.e1, m->pix));
-    for (int f = 0; f < nb && m->uy_out; f++) pack_422(m, sl[f]->uy_out, out_dev[f], out_pitch, s);
+    for (int f = 0; f < nb && m->conv_out; f++) conv_pack(m, sl[f]->conv_out, out_dev[f], out_pitch, s);
     if (outer) HIP_CHECK(hipEventRecord(ev.e1, s));
     ev.keep();
     for (int f = 0; f < nb; f++) finish_slot(*sl[f], s);

@@ -6,10 +6,8 @@
 #include <utility>
 #include <vector>
 
+#include "frame_layout.hpp"
 #include "host_common.hpp"
-#include "uyvy_host.hpp"
-#include "yuv422_host.hpp"
-#include "yuv10_host.hpp"
 
 // =================================================================================================
 // Mapper (vr::Mapper)
@@ -65,19 +63,19 @@ struct octvr_mapper {
         uint32_t* tickets = nullptr;           // 8 per-XCD + 1 global last-workgroup-done counters
         uint32_t* queue = nullptr;
         hipEvent_t done = nullptr;  // recorded after the slot's last stitch (its stream may since be gone)
-        const octvr::FootFrames* uy_in = nullptr;  // UYVY input: the slot's 4:2:0 frame per camera (SlotBufs)
-        uint8_t* uy_out = nullptr;                 // UYVY output: the slot's 4:2:0 output frame
+        const octvr::FootFrames* conv_in = nullptr;  // converted input: the slot's NV12 frame per camera (SlotBufs)
+        uint8_t* conv_out = nullptr;                 // converted output: the slot's NV12 output frame
     };
     struct SlotBufs {
         DevBuf<double> gains;
         DevBuf<unsigned long long> totals;
         DevBuf<uint32_t> tickets, queue;
-        // Packed UYVY 4:2:2 sides (octvr_mapper_set_pixel_formats): one NV12 frame per camera (pitch = width)
-        // that the slot's unpack launch fills inside the footprint and every stage of the stitch reads, and
-        // one NV12 output frame (SW x 3 SH / 2) the stitch writes and the pack launch reads
-        std::vector<DevBuf<uint8_t>> uy_in;
-        octvr::FootFrames uy_frames{};
-        DevBuf<uint8_t> uy_out;
+        // Converted sides (octvr_mapper_set_pixel_formats): one NV12 frame per camera (pitch = width) that the
+        // slot's unpack launch fills inside the footprint and every stage of the stitch reads, and one NV12
+        // output frame (SW x 3 SH / 2) the stitch writes and the pack launch reads
+        std::vector<DevBuf<uint8_t>> conv_in;
+        octvr::FootFrames conv_frames{};
+        DevBuf<uint8_t> conv_out;
     };
     std::vector<FrameSlot> slots;
     std::vector<std::unique_ptr<SlotBufs>> slot_bufs;  // owners of the slots' buffers, slot by slot
@@ -85,17 +83,16 @@ struct octvr_mapper {
     int timing = 0;             // event-timing period in stitches (0 = off)
     uint64_t timed_calls = 0;
     int pix = 0;                // layouts of the inputs and the output (octvr_mapper_set_pixel_formats): kPixInNv12 | kPixOutNv12
-    // Packed UYVY 4:2:2 on either side (mapper_set_uyvy): the stitch itself then runs on the frame slot's NV12
-    // frames (`pix` carries NV12 for that side); uy_table: the unpack kernel's pieces over this mapper's footprint
-    // The other 4:2:2 layouts (YUYV, YUV422P, NV16; yuv422.hip) share all of it — the slot frames, the table, the
-    // footprint runs: uy_in / uy_out say that the side is 4:2:2, fmt422_in / fmt422_out which layout
-    // (OCTVR_PIX_UYVY422 .. OCTVR_PIX_NV16; 0: the side is 4:2:0).  So do the 10-bit layouts (OCTVR_PIX_P010 ..
-    // OCTVR_PIX_YUV422P10; yuv10.hip): a converted side like a 4:2:2 one, 4:2:0 or not
-    bool uy_in = false, uy_out = false;
-    int fmt422_in = 0, fmt422_out = 0;
-    DevBuf<octvr::UyvyRun> uy_table;
-    size_t uy_runs = 0, uy_in_bytes = 0;
-    std::vector<octvr::FootRun> uy_foot_runs;  // the runs the table was cut from (octvr_debug_mapper_uyvy_runs)
+    // A converted capture layout on either side (mapper_set_conv; frame_layout.hpp): the stitch itself then runs
+    // on the frame slot's NV12 frames (`pix` carries NV12 for that side).  conv_fmt_in / conv_fmt_out: the side's
+    // OCTVR_PIX_* value (0: the side is 8-bit 4:2:0, conv_in / conv_out false); conv_table: the unpack kernel's
+    // pieces over this mapper's footprint, the same for every layout (the sources are frames: no piece's `off` is
+    // read); conv_in_px: the pixels of the pieces' rows, run_bpp() packed bytes each.
+    bool conv_in = false, conv_out = false;
+    int conv_fmt_in = 0, conv_fmt_out = 0;
+    DevBuf<octvr::ConvRun> conv_table;
+    size_t conv_runs = 0, conv_in_px = 0;
+    std::vector<octvr::FootRun> conv_foot_runs;  // the runs the table was cut from (octvr_debug_mapper_uyvy_runs)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events, free_events;  // recorded / reusable
     ~octvr_mapper() {
         for (auto& sl : slots)
@@ -130,23 +127,10 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
 // from: its size, counts and ROIs are checked, its maps are the caller's contract); 0, 0 drops the list.
 // Synchronizes the mapper.  OCTVR_E_UNSUPPORTED for a blended or scaled mapper.
 void mapper_prepare_preview(octvr_mapper* m, const octvr_rig* rig, int w, int h);
-// The packed UYVY sides (octvr_mapper_set_pixel_formats): allocates or frees every frame slot's 4:2:0 frames and
+// The converted sides (octvr_mapper_set_pixel_formats): allocates or frees every frame slot's NV12 frames and
 // builds the unpack table from the mapper's footprint.  The mapper is synchronized by the caller.
-// in / out: the side's converted format (OCTVR_PIX_UYVY422, _YUYV422, _YUV422P, _NV16, or a 10-bit one) or 0 for
-// an 8-bit 4:2:0 side.
-void mapper_set_uyvy(octvr_mapper* m, int in, int out);
-// A format whose side is converted to or from the slot's NV12 frames.
-inline bool converted_format(int f) { return f == OCTVR_PIX_UYVY422 || octvr::yuv422_format(f) || octvr::yuv10_format(f); }
-// Bytes of a row and rows of a w x h frame in a 4:2:2 or 10-bit format.
-inline size_t frame422_row_bytes(int fmt, int w) {
-    return (fmt == OCTVR_PIX_UYVY422 || fmt == OCTVR_PIX_YUYV422 || octvr::yuv10_format(fmt) ? 2 : 1) * (size_t)w;
-}
-inline size_t frame422_rows(int fmt, int h) {
-    if (octvr::yuv10_format(fmt)) return (size_t)octvr::yuv10_frame_rows(fmt - octvr::kYuv10First, h);
-    return (fmt == OCTVR_PIX_UYVY422 || fmt == OCTVR_PIX_YUYV422 ? 1 : 2) * (size_t)h;
-}
-// A 10-bit frame's samples are 16-bit words: its base and pitch are multiples of 2.
-inline bool yuv10_aligned(const void* base, size_t pitch) { return ((reinterpret_cast<uintptr_t>(base) | pitch) & 1u) == 0; }
+// in / out: the side's converted format (frame_layout.hpp converted_format) or 0 for an 8-bit 4:2:0 side.
+void mapper_set_conv(octvr_mapper* m, int in, int out);
 // Consecutive set groups of a footprint as runs, gaps of up to `gap` groups bridged; bytes: their 4:2:0 size.
 constexpr int kRunGap = 2;
 std::vector<FootRun> footprint_runs(const SourceFootprint& f, size_t& bytes, int gap = kRunGap);

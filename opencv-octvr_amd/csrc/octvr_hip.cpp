@@ -390,10 +390,8 @@ int octvr_mapper_set_pixel_formats(octvr_mapper* m, int in_format, int out_forma
                 "OCTVR_PIX_YUV422P10");
         DeviceGuard dg(m->device);
         mapper_sync(*m);  // stitches in flight keep the layouts they were issued with
-        // a packed UYVY side is converted to or from NV12 frames of the frame slot: the stitch sees NV12 there
-        // (so is a side in any other 4:2:2 layout, or in a 10-bit one)
-        auto is422 = [](int f) { return converted_format(f); };
-        mapper_set_uyvy(m, is422(in_format) ? in_format : 0, is422(out_format) ? out_format : 0);
+        // a side in a converted layout is converted to or from NV12 frames of the frame slot: the stitch sees NV12 there
+        mapper_set_conv(m, converted_format(in_format) ? in_format : 0, converted_format(out_format) ? out_format : 0);
         m->pix = (in_format != OCTVR_PIX_YUV420P ? kPixInNv12 : 0) | (out_format != OCTVR_PIX_YUV420P ? kPixOutNv12 : 0);
     });
 }
@@ -401,8 +399,8 @@ int octvr_mapper_set_pixel_formats(octvr_mapper* m, int in_format, int out_forma
 int octvr_mapper_pixel_formats(const octvr_mapper* m, int* in_format, int* out_format) {
     return guarded([&] {
         REQUIRE(m && in_format && out_format, "NULL argument");
-        *in_format = m->uy_in ? m->fmt422_in : (m->pix & kPixInNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
-        *out_format = m->uy_out ? m->fmt422_out : (m->pix & kPixOutNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
+        *in_format = m->conv_in ? m->conv_fmt_in : (m->pix & kPixInNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
+        *out_format = m->conv_out ? m->conv_fmt_out : (m->pix & kPixOutNv12) ? OCTVR_PIX_NV12 : OCTVR_PIX_YUV420P;
     });
 }
 
@@ -511,24 +509,22 @@ int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
         std::string js = tmp;
         js += ", \"preview_prepared\": [" + std::to_string(m->pv.view.dw) + ", " + std::to_string(m->pv.view.dh) +
               "], \"preview_entries\": " + std::to_string(m->pv.view.n_entries);
-        // packed UYVY sides: the footprint runs the unpack launch converts and the packed bytes it reads per
-        // frame, the packed bytes the pack launch writes (0: that side is not UYVY)
-        const bool uy_i = m->uy_in && m->fmt422_in == OCTVR_PIX_UYVY422, uy_o = m->uy_out && m->fmt422_out == OCTVR_PIX_UYVY422;
-        js += ", \"uyvy_runs\": " + std::to_string(uy_i ? m->uy_runs : 0) +
-              ", \"uyvy_in_bytes\": " + std::to_string(uy_i ? m->uy_in_bytes : 0) +
-              ", \"uyvy_out_bytes\": " + std::to_string(uy_o ? (size_t)2 * m->SW * m->SH : 0);
-        // the same three figures for a YUYV, YUV422P or NV16 side (every 4:2:2 layout is 2 bytes per pixel)
-        const bool y2_i = m->uy_in && yuv422_format(m->fmt422_in), y2_o = m->uy_out && yuv422_format(m->fmt422_out);
-        js += ", \"yuv422_runs\": " + std::to_string(y2_i ? m->uy_runs : 0) +
-              ", \"yuv422_in_bytes\": " + std::to_string(y2_i ? m->uy_in_bytes : 0) +
-              ", \"yuv422_out_bytes\": " + std::to_string(y2_o ? (size_t)2 * m->SW * m->SH : 0);
-        // a 10-bit side: 6 (4:2:0) or 8 (4:2:2) bytes per pixel of a footprint piece's row against UYVY's 4, and
-        // 3 or 4 bytes per output pixel
-        const bool t_i = m->uy_in && yuv10_format(m->fmt422_in), t_o = m->uy_out && yuv10_format(m->fmt422_out);
-        js += ", \"yuv10_runs\": " + std::to_string(t_i ? m->uy_runs : 0) + ", \"yuv10_in_bytes\": " +
-              std::to_string(t_i ? m->uy_in_bytes / 4 * (size_t)yuv10_run_bpp(m->fmt422_in - kYuv10First) : 0) +
-              ", \"yuv10_out_bytes\": " +
-              std::to_string(t_o ? (size_t)2 * m->SW * frame422_rows(m->fmt422_out, m->SH) : 0);
+        // converted sides, per family of layouts (0: the side is not of the family): the footprint runs the unpack
+        // launch converts and the packed bytes it reads per frame (run_bpp(): 4, 6 or 8 per pixel of a piece's row),
+        // the bytes of the frame the pack launch writes
+        const LayoutDesc li = layout_of(m->conv_in ? m->conv_fmt_in : 0), lo = layout_of(m->conv_out ? m->conv_fmt_out : 0);
+        const struct {
+            const char* prefix;
+            bool (*is)(int pix, const LayoutDesc& d);
+        } families[] = {{"uyvy", [](int pix, const LayoutDesc&) { return pix == OCTVR_PIX_UYVY422; }},
+                        {"yuv422", [](int pix, const LayoutDesc& d) { return d.bytes == 1 && pix != OCTVR_PIX_UYVY422; }},
+                        {"yuv10", [](int, const LayoutDesc& d) { return d.bytes == 2; }}};
+        for (const auto& f : families) {
+            const bool i = f.is(m->conv_fmt_in, li), o = f.is(m->conv_fmt_out, lo);
+            js += std::string(", \"") + f.prefix + "_runs\": " + std::to_string(i ? m->conv_runs : 0) + ", \"" + f.prefix +
+                  "_in_bytes\": " + std::to_string(i ? m->conv_in_px * (size_t)li.run_bpp() : 0) + ", \"" + f.prefix +
+                  "_out_bytes\": " + std::to_string(o ? (size_t)lo.row_bytes(m->SW) * (size_t)lo.rows(m->SH) : 0);
+        }
         if (m->mb) js += ", " + multiband_info(*m->mb);
         else if (!m->tiles.stats.empty()) js += ", " + m->tiles.stats + ", \"items_packed\": " + std::to_string(m->tiles.n_packed);
         js += "}";

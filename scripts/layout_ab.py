@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""What the 10-bit layouts cost on the C2 rig (BASELINE.json configs[1]): the bench's frame sets stitched with each of
-"uyvy422" (the 8-bit yardstick: uyvy.hip's kernels), "p010", "yuv420p10", "p210" and "yuv422p10" on both sides, the
-formats interleaved, `--rounds` times `--steps` stitches each at one frame in flight.  Per format it prints one JSON
-line with the stitch's own HIP-event times (octvr_mapper_set_timing: the events bracket the unpack, the stitch and the
-pack) in three configurations — format in and out, in only, out only — and the planar stitch timed the same way,
-so unpack = in-only - planar and pack = out-only - planar (medians), next to the bytes the conversions move
+"""What the converted capture layouts cost on the C2 rig (BASELINE.json configs[1]): the bench's frame sets stitched
+with each of "uyvy422", "yuyv422", "yuv422p", "nv16", "p010", "yuv420p10", "p210" and "yuv422p10" (frame_layout.hip's
+kernels), the formats interleaved, `--rounds` times `--steps` stitches each at one frame in flight.  Per format it
+prints one JSON line with the stitch's own HIP-event times (octvr_mapper_set_timing: the events bracket the unpack, the
+stitch and the pack) in three configurations — format in and out, in only, out only — and the planar stitch timed the
+same way, so unpack = in-only - planar and pack = out-only - planar (medians), next to the bytes the conversions move
 (octvr_mapper_info).  Before the runs, the full-size parity of every layout: in and out equals the planar stitch of
-the same pixels rearranged by the two rules (torch, on the device).  --out appends the lines to a file."""
+the same pixels rearranged by the two rules (torch, on the device).  --out appends the lines to a file.
+--formats restricts the run to some of the layouts."""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -18,29 +20,35 @@ for p in (ROOT, os.path.join(ROOT, "opencv-octvr_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-FORMATS = ["uyvy422", "p010", "yuv420p10", "p210", "yuv422p10"]
+FORMATS = ["uyvy422", "yuyv422", "yuv422p", "nv16", "p010", "yuv420p10", "p210", "yuv422p10"]
+# the prefix of a format's octvr_mapper_info keys
+INFO_PREFIX = {"uyvy422": "uyvy", "yuyv422": "yuv422", "yuv422p": "yuv422", "nv16": "yuv422", "p010": "yuv10", "yuv420p10": "yuv10",
+               "p210": "yuv10", "yuv422p10": "yuv10"}
 
 
 def to_format(fmt, t, w, h):
-    """"Y over [U|V]" -> layout fmt by the output rule, on the device (bytes)."""
+    """"Y over [U|V]" -> layout fmt by the output rule (a 4:2:2 layout carries every chroma row on two rows; a 10-bit
+    sample is the byte << 2 in its word's bits 9..0 or 15..6), on the device (bytes)."""
     import torch
     u, v = t[h:, :w // 2], t[h:, w // 2:w]
-    if fmt == "uyvy422":
-        out = torch.empty((h, 2 * w), dtype=torch.uint8, device=t.device)
-        out[:, 1::2] = t[:h, :w]
-        out[:, 0::4] = u.repeat_interleave(2, dim=0)
-        out[:, 2::4] = v.repeat_interleave(2, dim=0)
-        return out
-    c422, planar = fmt in ("p210", "yuv422p10"), fmt in ("yuv420p10", "yuv422p10")
-    if c422:
+    if fmt not in ("p010", "yuv420p10"):
         u, v = u.repeat_interleave(2, dim=0), v.repeat_interleave(2, dim=0)
-    words = torch.empty((2 * h if c422 else h * 3 // 2, w), dtype=torch.int16, device=t.device)
-    words[:h] = t[:h, :w].to(torch.int16)
-    if planar:
-        words[h:, :w // 2], words[h:, w // 2:] = u.to(torch.int16), v.to(torch.int16)
+    if fmt in ("uyvy422", "yuyv422"):
+        out = torch.empty((h, 2 * w), dtype=torch.uint8, device=t.device)
+        y0 = 1 if fmt == "uyvy422" else 0
+        out[:, y0::2] = t[:h, :w]
+        out[:, 1 - y0::4] = u
+        out[:, 3 - y0::4] = v
+        return out
+    out = torch.empty((h + u.shape[0], w), dtype=torch.uint8, device=t.device)
+    out[:h] = t[:h, :w]
+    if fmt in ("yuv422p", "yuv420p10", "yuv422p10"):
+        out[h:, :w // 2], out[h:, w // 2:] = u, v
     else:
-        words[h:, 0::2], words[h:, 1::2] = u.to(torch.int16), v.to(torch.int16)
-    return (words << (2 if planar else 8)).view(torch.uint8)  # little-endian words as bytes
+        out[h:, 0::2], out[h:, 1::2] = u, v
+    if fmt in ("yuv422p", "nv16"):
+        return out
+    return (out.to(torch.int16) << (2 if fmt in ("yuv420p10", "yuv422p10") else 8)).view(torch.uint8)  # little-endian words
 
 
 def main():
@@ -49,8 +57,10 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--frame-sets", type=int, default=4)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--formats", default=",".join(FORMATS))
     args = ap.parse_args()
 
+    formats = [k for k in FORMATS if k in args.formats.split(",")]
     import torch
     import bench
     import octvr_amd as ox
@@ -66,28 +76,30 @@ def main():
             for i, (w, h) in enumerate(sizes)]
     planar = [base] + [bench.derive_set(base, [bench.frame_seed(0, j, i) for i in range(len(sizes))])
                        for j in range(1, nsets)]
-    sets = {k: [[to_format(k, t, w, h) for t, (w, h) in zip(fs, sizes)] for fs in planar] for k in FORMATS}
+    sets = {k: [[to_format(k, t, w, h) for t, (w, h) in zip(fs, sizes)] for fs in planar] for k in formats}
     sets["yuv420p"] = planar
-    outs = {k: torch.empty(ox.frame_shape(k, W, H), dtype=torch.uint8, device=f"cuda:{dev}") for k in FORMATS + ["yuv420p"]}
+    outs = {k: torch.empty(ox.frame_shape(k, W, H), dtype=torch.uint8, device=f"cuda:{dev}") for k in formats + ["yuv420p"]}
     ref = outs["yuv420p"]
 
     m.stitch(planar[1], ref)
     torch.cuda.synchronize(dev)
     g_planar = m.gains()
-    info = {"metric": "yuv10_parity_C2", "so_sha256": bench.lib_sha256(), "footprint_bytes": m.info()["footprint_bytes"],
+    with open(ox.LIB_PATH, "rb") as f:  # the library in use (OCTVR_HIP_LIB selects another build for an A/B)
+        so_sha256 = hashlib.sha256(f.read()).hexdigest()
+    info = {"metric": "layout_parity_C2", "so_sha256": so_sha256, "footprint_bytes": m.info()["footprint_bytes"],
             "out_420_bytes": W * H * 3 // 2}
     moved = {}
-    for k in FORMATS:
+    for k in formats:
         m.set_pixel_formats(k, k)
         m.stitch(sets[k][1], outs[k])
         torch.cuda.synchronize(dev)
         ok = bool(torch.equal(outs[k], to_format(k, ref, W, H))) and m.gains() == g_planar
         i = m.info()
-        pre = "uyvy" if k == "uyvy422" else "yuv10"
+        pre = INFO_PREFIX[k]
         info["equal_" + k] = ok
         moved[k] = (i[pre + "_in_bytes"] + info["footprint_bytes"], i[pre + "_out_bytes"] + info["out_420_bytes"])
         if not ok:
-            raise SystemExit("yuv10_ab: the %s output differs from the rearranged planar output" % k)
+            raise SystemExit("layout_ab: the %s output differs from the rearranged planar output" % k)
     lines = [info]
     print(json.dumps(info), flush=True)
 
@@ -95,7 +107,7 @@ def main():
     times = {}
     m.set_timing(1)
     for rnd in range(args.rounds):
-        for k in ["yuv420p"] + FORMATS:
+        for k in ["yuv420p"] + formats:
             for name, pair in (configs if k != "yuv420p" else [("both", lambda k: (k, k))]):
                 fi, fo = pair(k)
                 m.set_pixel_formats(fi, fo)
@@ -110,9 +122,9 @@ def main():
     m.set_timing(0)
     med = {key: statistics.median(v) * 1e3 for key, v in times.items()}  # us: the median round's mean
     base_us = med[("yuv420p", "both")]
-    for k in FORMATS:
+    for k in formats:
         unpack, pack = med[(k, "in")] - base_us, med[(k, "out")] - base_us
-        d = {"metric": "yuv10_kernel_C2", "format": k, "rounds": len(times[(k, "in")]), "steps": args.steps, "planar_us": round(base_us, 2),
+        d = {"metric": "layout_kernel_C2", "format": k, "rounds": len(times[(k, "in")]), "steps": args.steps, "planar_us": round(base_us, 2),
              "in_us": round(med[(k, "in")], 2), "out_us": round(med[(k, "out")], 2), "both_us": round(med[(k, "both")], 2),
              "unpack_us": round(unpack, 2), "pack_us": round(pack, 2), "unpack_bytes": int(moved[k][0]),
              "pack_bytes": int(moved[k][1]), "unpack_tb_per_s": round(moved[k][0] / max(unpack, 1e-3) / 1e6, 3),
