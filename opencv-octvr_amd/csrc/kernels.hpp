@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "camera_math.hpp"
+#include "multiband_plan.hpp"
 
 namespace octvr {
 
@@ -102,7 +103,7 @@ __host__ __device__ inline TapCell tap_cell(uint32_t xy, int w, int h) {
 //   13-26 LDS byte offset of tap (x, y) (one v_bfe_u32); 27-29 zero; 30-31 slot (the slot's gain
 //   sits at byte offset e >> 27 of a 4-slot table of f32 pairs).  Three VALU decode a pixel's entry.
 // A pixel with no camera, or with every tap outside, is entry 0 and comes out black.
-constexpr int kTileW = 128, kTileH = 8, kTilePx = kTileW * kTileH;
+// (the tile, kTileW x kTileH = 128 x 8 pixels: multiband_plan.hpp)
 constexpr int kTileSlots = 4;
 // Items of the tiled composite: two vertically adjacent 128 x 8 tiles (128 x 16 pixels, 8 quads per lane).
 constexpr int kItemHalves = 2;
@@ -465,64 +466,8 @@ hipError_t launch_stitch_batch(const FrameSet* frames, int nf, const TiledLut& l
 // blend step reads are ever computed (tile lists built once per rig).  pyrUp is evaluated on the
 // fly from 3x3 source taps per output quad through per-row / per-column tap tables (UpQuad), which
 // encode pyr_up.cu's borders (abs, then clamp) and its 8-row-block quirk.
-constexpr int kMbMaxBands = 10;
-// pyrUp source patch of one 128x8 tile: <= 8 rows (4 quad rows, the row quirk, any block phase)
-// by <= 72 columns (64 quad columns + borders), staged in LDS
-constexpr int kUpPatchRows = 8, kUpPatchCols = 72;
-struct alignas(16) UpQuad {  // one quad row (or column) of a pyrUp output; 16 B: one load per lane
-    uint16_t idx[3];      // source rows (cols) of the 3 union taps, clamped, local to the coarser level
-    uint16_t pad0;
-    uint8_t w0[3], w1[3]; // integer weights of the quad's first / second row (col) over them
-    uint8_t pad1[2];
-};
-static_assert(sizeof(UpQuad) == 16, "UpQuad layout");
-
-// The same taps computed in registers instead of read from the UpQuad tables (no dependent table
-// load between the camera record and the tap loads).  For the quad at even level-grid index g, local
-// pixels o0 = g - off and o0 + 1 (up_taps / up_table in multiband_host.cpp, pyr_up.cu:55-166):
-//   o0 even (o0 = 2h):   sources h-1, h, h+1+k   w0 = 1 6 1, w1 = 0 4 4    k: rows, o0 % 8 == 6
-//   o0 odd  (o0 = 2h+1): sources h, h+1, h+2+k'  w0 = 4 4 0, w1 = 1 6 1    k': rows, o0 % 8 == 5
-//                                   (rows, o0 % 8 == 7: the odd pixel reads h, h+2: w0 = 4 0 4)
-// A pixel outside [0, n_local) weighs 0; sources are |u| clamped to n_src - 1.  Zero-weight slots
-// may hold a different (in-range) source than the table's, so the weighted sums are identical.
-__host__ __device__ inline int up_clamp(int u, int n_src) {
-    u = u < 0 ? -u : u;
-    return u < n_src - 1 ? u : n_src - 1;
-}
-struct UpArith {
-    int idx[3];
-    int w0[3], w1[3];
-};
-__host__ __device__ inline UpArith up_arith(int g, int off, int n_local, int n_src, bool rows) {
-    UpArith e;
-    const int o0 = g - off;
-    const int h = o0 >> 1;  // floor
-    const bool odd = (o0 & 1) != 0;
-    const int m8 = o0 & 7;
-    const bool v0 = o0 >= 0 && o0 < n_local, v1 = o0 + 1 >= 0 && o0 + 1 < n_local;
-    int u0, u2;
-    if (!odd) {
-        u0 = h - 1;
-        u2 = h + 1 + ((rows && m8 == 6) ? 1 : 0);
-        e.w0[0] = 1, e.w0[1] = 6, e.w0[2] = 1;
-        e.w1[0] = 0, e.w1[1] = 4, e.w1[2] = 4;
-    } else {
-        u0 = h;
-        u2 = h + 2 + ((rows && m8 == 5) ? 1 : 0);
-        const bool q7 = rows && m8 == 7;
-        e.w0[0] = 4, e.w0[1] = q7 ? 0 : 4, e.w0[2] = q7 ? 4 : 0;
-        e.w1[0] = 1, e.w1[1] = 6, e.w1[2] = 1;
-    }
-    e.idx[0] = up_clamp(u0, n_src);
-    e.idx[1] = up_clamp(u0 + 1, n_src);
-    e.idx[2] = up_clamp(u2, n_src);
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        e.w0[j] = v0 ? e.w0[j] : 0;
-        e.w1[j] = v1 ? e.w1[j] : 0;
-    }
-    return e;
-}
+// (kMbMaxBands, the staged patch kUpPatchRows x kUpPatchCols, UpQuad and the register taps up_arith:
+// multiband_plan.hpp, which also builds the tables)
 
 struct MbCamLevel {       // one camera at one level
     uint32_t g_off;        // byte offset of the camera's G in the level's pyramid allocation
@@ -553,16 +498,8 @@ struct RgbaOut {
     uint32_t res_pitch, res_u_off, res_v_off;
     int res_rgba;
 };
-// Sub-tiles: 32 x 8 quarters of a 128 x 8 tile (one mb_blend wave each; lane = quad).  The multi-band
-// classification (owned / deep / unread / result, multiband_host.cpp) is per sub-tile, so a seam that
-// crosses a tile leaves its other quarters on the cheap paths.
-constexpr int kSubW = 32, kSubs = kTileW / kSubW;
-// Per-item flags of the MODE-1 remap (bits 8-23 of the item header's device word 2, see
-// TiledLutDev::upload; bits 8-15 of a wide tile's camera word, for its one half): for half h and quarter q,
-// bit 4h + q: that sub-tile's final result is written by the remap (its one deep camera's G0 converted),
-// bit 8 + 4h + q: its G0 is written (some pyrDown or blend reads it).  Items of <= 2 halves.
-__host__ __device__ constexpr uint32_t item_result_bit(int h, int q) { return 1u << (4 * h + q); }
-__host__ __device__ constexpr uint32_t item_g0_bit(int h, int q) { return 1u << (8 + 4 * h + q); }
+// (the 32 x 8 sub-tiles kSubW / kSubs, their classification and the remap items' item_result_bit /
+// item_g0_bit: multiband_plan.hpp)
 constexpr uint32_t kItemAllG0 = 0xFF00u;
 
 hipError_t launch_mb_remap(const FrameSet& frames, const TiledLut& lut, const double* gains, int use_gain,
@@ -607,10 +544,6 @@ struct MbBlendArgs {
 hipError_t launch_mb_blend(const MbBlendArgs& a, hipStream_t s);
 // Build time: K4 pyrDown<float, BrdReflect101> with nvcc's FMA contraction (pyr_down.cu:55-192).
 hipError_t launch_pyr_down_f32(const float* src, int sw, int sh, float* dst, int dw, int dh, hipStream_t s);
-// Build time: blocks[by * bx_n + bx] = 1 for every 8x8 block of the level grid where the camera's
-// weight is non-zero (level 0: u8 seam, else f32).
-hipError_t launch_block_activity(const void* weight, int is_u8, int w, int h, int ox, int oy, int bx_n, uint8_t* blocks,
-                                 hipStream_t s);
 
 hipError_t launch_remap_u8(const uint8_t* src, int sw, int sh, int64_t spitch, int cn, const float* map1,
                            const float* map2, int mw, int mh, int64_t mpitch, float scale_x, float scale_y,

@@ -273,7 +273,7 @@ __global__ void __launch_bounds__(256, kBlendWaves) mb_blend_kernel(MbBlendArgs 
     // the f32 pyramid's 1.0f above; tile_owned): D = G - pyrUp(G_next) (G at the top level) exactly,
     // the weight sum is kWsumOwned and rint(D * kRcpOwned) = D (|D| <= 255), so the Laplacian is taken
     // as is, with no weight loads or sums.
-    // Deep tiles (owned = 2, multiband_host.cpp): R = G on every pixel, by induction over the levels
+    // Deep tiles (owned = 2, mb_classify_deep in multiband_plan.hpp): R = G on every pixel, by induction over the levels
     // above (one camera of weight 1 on all the pyrUp taps, with the camera's and the collapse's taps
     // identical), so neither pyrUp is taken.
     const int own = a.work ? (int)(wk.x >> 27) : a.owned != nullptr ? uniform((int)a.owned[tile]) : 0;
@@ -472,8 +472,8 @@ __global__ void __launch_bounds__(256, kBlendWaves) mb_blend_kernel(MbBlendArgs 
         };
         // x and y are even on the level grid: every quad has the even tap pattern (1 6 1 | 0 4 4) as
         // constants; the zero weights up_arith gives pixels outside the level only matter for pixels
-        // that are never stored (W, H even at level 0, feather's odd ROIs included: multiband_create's even
-        // grid; level > 0 stores valid pixels only)
+        // that are never stored (W, H even at level 0, feather's odd ROIs included: mb_plan_rects' even
+        // grid, multiband_plan.hpp; level > 0 stores valid pixels only)
         UpArith ur = up_arith(y, 0, a.H, a.H_next, true), uc = up_arith(x, 0, a.W, a.W_next, false);
 #pragma unroll
         for (int j = 0; j < 3; j++) {
@@ -570,35 +570,6 @@ hipError_t launch_pyr_down_f32(const float* src, int sw, int sh, float* dst, int
     if (total <= 0) return hipSuccess;
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 8);
     hipLaunchKernelGGL(pyr_down_f32_kernel, dim3(blocks), dim3(256), 0, s, src, sw, sh, dst, dw, dh);
-    return hipGetLastError();
-}
-
-// Build time: which 8x8 blocks of the level grid hold a non-zero weight of one camera.  A lane
-// scans the 8 pixels of one block row and marks the block (benign duplicate stores of 1).
-__global__ void __launch_bounds__(256) block_activity_kernel(const void* weight, int is_u8, int w, int h, int ox,
-                                                             int oy, int bx_n, uint8_t* blocks) {
-    const int gx_n = (w + 7 + (ox & 7)) / 8 + 1;  // 8-pixel groups per row on the level grid
-    const int64_t total = (int64_t)gx_n * h;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int yl = (int)(i / gx_n), gi = (int)(i - (int64_t)yl * gx_n);
-        const int gx0 = ((ox >> 3) + gi) * 8;  // level-grid x of the group
-        bool nz = false;
-        for (int q = 0; q < 8; q++) {
-            const int xl = gx0 + q - ox;
-            if (xl < 0 || xl >= w) continue;
-            const int64_t k = (int64_t)yl * w + xl;
-            nz |= is_u8 ? static_cast<const uint8_t*>(weight)[k] != 0 : static_cast<const float*>(weight)[k] != 0.f;
-        }
-        if (nz) blocks[(int64_t)((yl + oy) >> 3) * bx_n + (gx0 >> 3)] = 1;
-    }
-}
-
-hipError_t launch_block_activity(const void* weight, int is_u8, int w, int h, int ox, int oy, int bx_n, uint8_t* blocks,
-                                 hipStream_t s) {
-    if (w <= 0 || h <= 0) return hipSuccess;
-    const int64_t total = (int64_t)((w + 7 + (ox & 7)) / 8 + 1) * h;
-    const int blocks_n = (int)std::min<int64_t>((total + 255) / 256, 256 * 8);
-    hipLaunchKernelGGL(block_activity_kernel, dim3(blocks_n), dim3(256), 0, s, weight, is_u8, w, h, ox, oy, bx_n, blocks);
     return hipGetLastError();
 }
 
