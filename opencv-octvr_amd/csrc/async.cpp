@@ -30,10 +30,13 @@
 //     the caller's device frames in place and one kernel (async_merge.hip) places the region frames into the
 //     caller's merged device frame; such frames travel the same queues, so pop order is push order;
 //   * the inputs may be in a converted capture layout (frame_layout.hpp: packed UYVY 4:2:2, what capture cards
-//     deliver, YUYV, YUV422P, NV16 and the 10-bit P010, YUV420P10, P210, YUV422P10): the footprint runs of the
-//     layout's planes copied and uploaded at the layout's 4, 6 or 8 B per pixel of a run's row (pack_run,
-//     run_table), and one kernel (frame_layout.hip) converts them into the slot's NV12 device frames — once for all
-//     mappers, which stay on NV12 input; device frames are converted the same way from the caller's frames.
+//     deliver, YUYV, YUV422P, NV16 and the 10-bit P010, YUV420P10, P210, YUV422P10): one kernel (frame_layout.hip)
+//     converts the uploaded runs into the slot's NV12 device frames — once for all mappers, which stay on NV12
+//     input; device frames are converted the same way from the caller's frames.
+// Every input layout takes the same host path: a table of footprint runs with their places in the packed buffer
+// (RunPlan: the native layouts' at 3 B per pixel of a run's row, a converted layout's run_table at 4, 6 or 8), one
+// pack_run per run, one upload, one unpack launch.  Every output path places a region's pieces by one table
+// (async_host.hpp region_pieces).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -242,7 +245,7 @@ struct octvr_async {
     // layouts of the host planes (octvr_async_set_pixel_formats); the mappers carry the same pair.  Written by
     // the caller's thread with no frame pending, read by the stages while a frame is
     int in_fmt = OCTVR_PIX_YUV420P, out_fmt = OCTVR_PIX_YUV420P;
-    int out_planes_used() const { return out_fmt == OCTVR_PIX_NV12 ? 2 : 3; }
+    int out_planes_used() const { return layout_of(out_fmt).planes(); }
     // preview (async.cpp:73-76): preview_w x preview_h RGB; per mapper its rectangle (w or h <= 0: none)
     int preview_w = 0, preview_h = 0;
     std::vector<Rect> preview_rects;
@@ -261,20 +264,35 @@ struct octvr_async {
     std::chrono::steady_clock::time_point fps_t = std::chrono::steady_clock::now();
     int64_t frame_count = 0;
     double frame_total_ms = 0, frame_fps = 0;
-    std::vector<FootRun> runs;  // what the mappers read of the inputs (footprint_runs)
-    size_t packed_bytes = 0;
-    DevBuf<FootRun> runs_dev;
-    // a converted input layout: the unpack kernel's pieces over the same runs with their places in the packed
-    // buffers (run_table), built when such a format is first set and again when conv_bpp changes
+    // What a frame uploads: the runs with their places in the packed buffers, the same table on the device for the
+    // unpack launch, and the packed bytes.  native: what the mappers read of the inputs (footprint_runs), for both
+    // 4:2:0 layouts; conv: the unpack kernel's pieces over the same runs (run_table), built when a converted format is
+    // first set and again when conv_bpp changes.
+    struct RunPlan {
+        std::vector<FootRun> runs;
+        DevBuf<FootRun> dev;
+        size_t bytes = 0;
+    };
+    RunPlan native, conv;
+    int conv_bpp = 0;  // packed bytes per pixel of a piece's row conv's offsets were built with (0: no table)
     bool in_conv() const { return converted_format(in_fmt); }
-    // the unpack launch of the input format over the table, from the packed buffer or the caller's frames
+    const RunPlan& plan() const { return in_conv() ? conv : native; }
+    // the unpack launch of a converted input format over its table, from the packed buffer or the caller's frames
     void conv_unpack(const ConvSources& src, const FootFrames& frames, hipStream_t s) {
-        HIP_CHECK(launch_layout_unpack(in_fmt, conv_table_dev.p, (int)conv_table.size(), src, frames, s));
+        HIP_CHECK(launch_layout_unpack(in_fmt, conv.dev.p, (int)conv.runs.size(), src, frames, s));
     }
-    std::vector<ConvRun> conv_table;
-    size_t conv_packed_bytes = 0;
-    int conv_bpp = 0;  // packed bytes per pixel of a piece's row the table's offsets were built with (0: no table)
-    DevBuf<ConvRun> conv_table_dev;
+    // the input format's launch that puts a slot's uploaded runs in place in its device frames
+    void unpack_packed(const Slot& sl, hipStream_t s) {
+        if (!in_conv()) {
+            HIP_CHECK(launch_unpack_runs_layout(sl.packed_dev.p, native.dev.p, (int)native.runs.size(), sl.frames,
+                                                in_fmt == OCTVR_PIX_NV12, s));
+            return;
+        }
+        ConvSources src;
+        memset(&src, 0, sizeof src);
+        src.packed = sl.packed_dev.p;
+        conv_unpack(src, sl.frames, s);
+    }
     Slot slots[kSlots];
     // output plane sets the caller registered (octvr_async_register_output): page-locked, downloaded into
     struct RegOut {
@@ -299,6 +317,7 @@ struct octvr_async {
     int pending = 0;  // pushed, not popped (caller thread only)
     int64_t device_frames = 0;               // octvr_async_push_device calls that queued a frame (caller thread only)
     std::atomic<int64_t> merge_launches{0};  // merge_regions_kernel launches (compute thread)
+    RegionPieces pieces(size_t k) const { return region_pieces(regions[k], regions_uv[k], out_fmt == OCTVR_PIX_NV12); }
     bool whole_frame_region() const {
         return regions.size() == 1 && regions[0].x == 0 && regions[0].y == 0 && regions[0].w == out_w && regions[0].h == out_h;
     }
@@ -335,24 +354,14 @@ struct octvr_async {
         if (j.device) return;  // the mappers read the caller's frames in place
         stage(j, [&] {
             uint8_t* const dst = slots[s].packed_host->p;
-            if (in_conv()) {
-                const LayoutDesc d = layout_of(in_fmt);
-                copy_in_pool.run(conv_table.size(), [&](size_t lo, size_t hi) {
-                    for (size_t k = lo; k < hi; k++) {
-                        const ConvRun& r = conv_table[k];
-                        const int i = (int)(r.cam & 31u);
-                        pack_run(d, dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng, &j.in_planes[3 * i],
-                                 &j.in_pitches[3 * i]);
-                    }
-                });
-                return;
-            }
+            const std::vector<FootRun>& runs = plan().runs;
+            const LayoutDesc d = layout_of(in_fmt);
             copy_in_pool.run(runs.size(), [&](size_t lo, size_t hi) {
                 for (size_t k = lo; k < hi; k++) {
                     const FootRun& r = runs[k];
                     const int i = (int)(r.cam & 31u);
-                    pack_run(dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng, &j.in_planes[3 * i],
-                             &j.in_pitches[3 * i], in_fmt == OCTVR_PIX_NV12);
+                    pack_run(d, dst + r.off, in_w[i], (int)(r.cam >> 8), (int)r.g0, (int)r.ng, &j.in_planes[3 * i],
+                             &j.in_pitches[3 * i]);
                 }
             });
         });
@@ -365,18 +374,9 @@ struct octvr_async {
         stage(j, [&] {
             DeviceGuard dg(device);
             Slot& sl = slots[j.slot];
-            if (in_conv()) {
-                if (conv_packed_bytes) {
-                    HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, conv_packed_bytes, hipMemcpyHostToDevice, up));
-                    ConvSources src;
-                    memset(&src, 0, sizeof src);
-                    src.packed = sl.packed_dev.p;
-                    conv_unpack(src, sl.frames, up);
-                }
-            } else if (packed_bytes) {
-                HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, packed_bytes, hipMemcpyHostToDevice, up));
-                HIP_CHECK(launch_unpack_runs_layout(sl.packed_dev.p, runs_dev.p, (int)runs.size(), sl.frames,
-                                                    in_fmt == OCTVR_PIX_NV12, up));
+            if (const size_t bytes = plan().bytes) {
+                HIP_CHECK(hipMemcpyAsync(sl.packed_dev.p, sl.packed_host->p, bytes, hipMemcpyHostToDevice, up));
+                unpack_packed(sl, up);
             }
             HIP_CHECK(hipStreamSynchronize(up));
         });
@@ -449,25 +449,15 @@ struct octvr_async {
                                              down));
                     continue;
                 }
-                // straight into the caller's registered planes: the region's Y rows, then its chroma rows'
-                // U (left) and V (right) halves (the device region is "Y over [U|V]", pitch = region width)
-                const Rect& r = regions[k];
-                const Rect& c = regions_uv[k];
-                const uint8_t* src = sl.out_dev[k].p;
-                HIP_CHECK(hipMemcpy2DAsync(j.out_planes[0] + (size_t)r.y * j.out_pitches[0] + r.x, j.out_pitches[0], src,
-                                           (size_t)r.w, (size_t)r.w, (size_t)r.h, hipMemcpyDeviceToHost, down));
-                if (out_fmt == OCTVR_PIX_NV12) {  // "Y over U,V pairs": whole chroma rows to byte column 2 c.x
-                    HIP_CHECK(hipMemcpy2DAsync(j.out_planes[1] + (size_t)c.y * j.out_pitches[1] + 2 * (size_t)c.x,
-                                               j.out_pitches[1], src + (size_t)r.h * r.w, (size_t)r.w, (size_t)r.w,
-                                               (size_t)c.h, hipMemcpyDeviceToHost, down));
-                    continue;
+                // straight into the caller's registered planes: the pieces of the device region frame, whose
+                // pitch is the region's width
+                const RegionPieces pc = pieces(k);
+                for (int i = 0; i < pc.n; i++) {
+                    const RegionPiece& p = pc.p[i];
+                    HIP_CHECK(hipMemcpy2DAsync(j.out_planes[p.plane] + p.y * j.out_pitches[p.plane] + p.x, j.out_pitches[p.plane],
+                                               sl.out_dev[k].p + p.src, (size_t)regions[k].w, p.bytes, p.rows,
+                                               hipMemcpyDeviceToHost, down));
                 }
-                HIP_CHECK(hipMemcpy2DAsync(j.out_planes[1] + (size_t)c.y * j.out_pitches[1] + c.x, j.out_pitches[1],
-                                           src + (size_t)r.h * r.w, (size_t)r.w, (size_t)c.w, (size_t)c.h,
-                                           hipMemcpyDeviceToHost, down));
-                HIP_CHECK(hipMemcpy2DAsync(j.out_planes[2] + (size_t)c.y * j.out_pitches[2] + c.x, j.out_pitches[2],
-                                           src + (size_t)r.h * r.w + r.w / 2, (size_t)r.w, (size_t)c.w, (size_t)c.h,
-                                           hipMemcpyDeviceToHost, down));
             }
             if (preview_w > 0)  // async.cpp:102-103
                 HIP_CHECK(hipMemcpyAsync(sl.preview_host->p, sl.preview_dev.p, sl.preview_host->n, hipMemcpyDeviceToHost,
@@ -482,24 +472,17 @@ struct octvr_async {
             if (j.direct || j.device) return;  // the D2H wrote the caller's planes / the frame stays on the device
             Slot& sl = slots[j.slot];
             for (size_t k = 0; k < mappers.size(); k++) {
-                const Rect& r = regions[k];
-                const Rect& c = regions_uv[k];
+                const RegionPieces pc = pieces(k);
+                const size_t w = (size_t)regions[k].w, luma_rows = pc.p[0].rows;
                 const uint8_t* src = sl.out_host[k]->p;
-                copy_out_pool.run((size_t)(r.h + c.h), [&](size_t lo, size_t hi) {
-                    for (size_t y = lo; y < hi; y++) {
-                        if (y < (size_t)r.h) {
-                            memcpy(j.out_planes[0] + (size_t)(r.y + (int)y) * j.out_pitches[0] + r.x, src + y * r.w, r.w);
-                        } else {
-                            const size_t cy = y - (size_t)r.h;
-                            const uint8_t* row = src + (size_t)(r.h + (int)cy) * r.w;
-                            if (out_fmt == OCTVR_PIX_NV12) {
-                                memcpy(j.out_planes[1] + (size_t)(c.y + (int)cy) * j.out_pitches[1] + 2 * (size_t)c.x, row,
-                                       r.w);
-                                continue;
-                            }
-                            memcpy(j.out_planes[1] + (size_t)(c.y + (int)cy) * j.out_pitches[1] + c.x, row, c.w);
-                            memcpy(j.out_planes[2] + (size_t)(c.y + (int)cy) * j.out_pitches[2] + c.x, row + r.w / 2, c.w);
-                        }
+                // the region's rows, luma then chroma, split over the pool: a chroma row is all chroma pieces' row
+                copy_out_pool.run(luma_rows + pc.p[1].rows, [&](size_t lo, size_t hi) {
+                    for (int i = 0; i < pc.n; i++) {
+                        const RegionPiece& p = pc.p[i];
+                        const size_t first = i ? luma_rows : 0;
+                        for (size_t y = std::max(lo, first); y < std::min(hi, first + p.rows); y++)
+                            memcpy(j.out_planes[p.plane] + (p.y + y - first) * j.out_pitches[p.plane] + p.x,
+                                   src + p.src + (y - first) * w, p.bytes);
                     }
                 });
             }
@@ -582,13 +565,16 @@ struct octvr_async {
 
 namespace {
 
-// The planes the output format uses (planar: Y, U, V; NV12: Y and the U,V plane of out_w bytes per row) are
-// there and wide enough; with NV12 the third entry is ignored.
-bool output_planes_ok(const octvr_async* a, uint8_t* const* planes, const size_t* pitches) {
-    const bool nv12 = a->out_fmt == OCTVR_PIX_NV12;
-    for (int k = 0; k < a->out_planes_used(); k++)
-        if (!planes[k] || pitches[k] < (size_t)(k && !nv12 ? a->out_w / 2 : a->out_w)) return false;
+// The host planes of a w-wide frame of the layout (frame_layout.hpp: planes(), plane_row_bytes) are there, wide
+// enough and, for 16-bit samples, at even addresses and pitches; entries past the layout's planes are ignored.
+template <class P>
+bool planes_ok(const LayoutDesc& d, int w, P* const* planes, const size_t* pitches) {
+    for (int k = 0; k < d.planes(); k++)
+        if (!planes[k] || pitches[k] < (size_t)d.plane_row_bytes(k, w) || !d.aligned(planes[k], pitches[k])) return false;
     return true;
+}
+bool output_planes_ok(const octvr_async* a, uint8_t* const* planes, const size_t* pitches) {
+    return planes_ok(layout_of(a->out_fmt), a->out_w, planes, pitches);
 }
 
 }  // namespace
@@ -675,13 +661,13 @@ int octvr_async_create_preview(const octvr_rig* const* rigs, int n_rigs, int dev
         SourceFootprint foot;
         foot.init(a->in_w, a->in_h);
         for (auto* m : a->mappers) foot.merge(mapper_footprint(m));
-        a->runs = footprint_runs(foot, a->packed_bytes);
-        REQUIRE(a->packed_bytes < ((size_t)1 << 32), "input footprint exceeds 4 GiB");
-        if (!a->runs.empty()) a->runs_dev.upload(a->runs.data(), a->runs.size());
+        a->native.runs = footprint_runs(foot, a->native.bytes);
+        REQUIRE(a->native.bytes < ((size_t)1 << 32), "input footprint exceeds 4 GiB");
+        if (!a->native.runs.empty()) a->native.dev.upload(a->native.runs.data(), a->native.runs.size());
         for (auto& sl : a->slots) {
             sl.packed_host.reset(new PinnedBuf());
-            sl.packed_host->alloc(std::max<size_t>(a->packed_bytes, 1));
-            sl.packed_dev.alloc(std::max<size_t>(a->packed_bytes, 1));
+            sl.packed_host->alloc(std::max<size_t>(a->native.bytes, 1));
+            sl.packed_dev.alloc(std::max<size_t>(a->native.bytes, 1));
             for (int i = 0; i < n_inputs; i++) {
                 const size_t bytes = (size_t)in_w[i] * (in_h[i] / 2 * 3);
                 sl.in_dev.emplace_back();
@@ -722,26 +708,11 @@ int octvr_async_push(octvr_async* a, const uint8_t* const* in_planes, const size
     auto j = std::make_shared<Job>();
     j->in_planes.assign(in_planes, in_planes + 3 * a->n_in);
     j->in_pitches.assign(in_pitches, in_pitches + 3 * a->n_in);
-    for (int i = 0; i < a->n_in; i++) {
-        const size_t w = (size_t)a->in_w[i];
-        const int f = a->in_fmt;
-        // a converted layout's planes (frame_layout.hpp pack_run): one packed plane; Y and a U,V plane; or Y, U
-        // and V with half a row's bytes each; planes of 16-bit words at even addresses and pitches
-        const LayoutDesc d = layout_of(f);
-        auto plane = [&](int k, size_t bytes) {
-            return in_planes[3 * i + k] && in_pitches[3 * i + k] >= bytes && d.aligned(in_planes[3 * i + k], in_pitches[3 * i + k]);
-        };
-        const size_t rb = (size_t)d.row_bytes((int)w);
-        const bool bad = d.converted() ? !(plane(0, rb) && (d.packed() || (d.halves() ? plane(1, rb / 2) && plane(2, rb / 2) : plane(1, rb))))
-                         : f == OCTVR_PIX_NV12
-                             ? !in_planes[3 * i] || !in_planes[3 * i + 1] || in_pitches[3 * i] < w || in_pitches[3 * i + 1] < w
-                             : !in_planes[3 * i] || !in_planes[3 * i + 1] || !in_planes[3 * i + 2] || in_pitches[3 * i] < w ||
-                                   in_pitches[3 * i + 1] < w / 2 || in_pitches[3 * i + 2] < w / 2;
-        if (bad) {
+    for (int i = 0; i < a->n_in; i++)
+        if (!planes_ok(layout_of(a->in_fmt), a->in_w[i], in_planes + 3 * i, in_pitches + 3 * i)) {
             set_last_error("bad input plane");
             return OCTVR_E_INVALID;
         }
-    }
     if (!output_planes_ok(a, out_planes, out_pitches)) {
         set_last_error("bad output plane");
         return OCTVR_E_INVALID;
@@ -761,25 +732,17 @@ int octvr_async_push_device(octvr_async* a, const uint8_t* const* in_dev, const 
                             size_t out_pitch, void* ready_event) {
     return guarded([&] {
         REQUIRE(a && in_dev && in_pitch && out_dev, "NULL argument");
-        REQUIRE(out_pitch >= (size_t)a->out_w, "output pitch smaller than width");
-        // the mappers' own limit (mapper.cpp check_out_pitch), and the merge's 32-bit offsets
-        REQUIRE((uint64_t)out_pitch * (uint64_t)(a->out_h + a->out_h / 2) < 0x7FFFFF80ull, "output frame larger than 2 GiB");
+        // the mappers' own limit (mapper.cpp check_out_frame), and the merge's 32-bit offsets
+        const char* why = frame_fault(layout_of(a->out_fmt), out_dev, out_pitch, a->out_w, a->out_h, 0x7FFFFF80ull);
+        REQUIRE(!why, std::string("output ") + why);
         REQUIRE(a->whole_frame_region() || (int)a->regions.size() <= kMergeMaxRegions,
                 "more regions than one merge launch takes");
         for (int i = 0; i < a->n_in; i++) {
-            REQUIRE(in_dev[i], "NULL input frame");
-            // the limits mapper_stitch sets (mapper.cpp checked_source_frame), refused here before anything is queued
-            if (a->in_conv()) {  // a whole frame of the layout, converted by the pipeline
-                const LayoutDesc d = layout_of(a->in_fmt);
-                REQUIRE(d.aligned(in_dev[i], in_pitch[i]), "10-bit input frames and pitches must be multiples of 2");
-                REQUIRE(in_pitch[i] >= (size_t)d.row_bytes(a->in_w[i]), "input pitch smaller than a row of the format");
-                REQUIRE((uint64_t)in_pitch[i] * (uint64_t)d.rows(a->in_h[i]) < 0x7FFFFFFFull, "input frame too large");
-                continue;
-            }
-            REQUIRE(in_pitch[i] >= (size_t)a->in_w[i], "input pitch smaller than width");
-            REQUIRE(in_pitch[i] < ((size_t)1 << 24) &&
-                        (uint64_t)in_pitch[i] * (uint64_t)(a->in_h[i] + a->in_h[i] / 2) < 0x7FFFFFFFull,
-                    "input frame too large");
+            // the limits mapper_stitch sets (mapper.cpp conv_sources, checked_source_frame), refused here before
+            // anything is queued
+            why = frame_fault(layout_of(a->in_fmt), in_dev[i], in_pitch[i], a->in_w[i], a->in_h[i], 0x7FFFFFFFull);
+            REQUIRE(!why, std::string("input ") + why);
+            REQUIRE(a->in_conv() || in_pitch[i] < ((size_t)1 << 24), "input pitch must be below 16 MiB");
         }
         // a host pointer (pinned memory included: the kernels could read it, slowly) is refused before any launch
         DeviceGuard dg(a->device);
@@ -849,10 +812,9 @@ int octvr_async_register_output(octvr_async* a, uint8_t* const* planes, const si
         // Planes of one allocation (a contiguous NV12 frame's Y and U,V; U and V as column halves of one
         // array) share pages or overlap: each page is locked once, through the merged range that holds it
         std::vector<PinRange> ranges;
-        const bool nv12 = a->out_fmt == OCTVR_PIX_NV12;
+        const LayoutDesc d = layout_of(a->out_fmt);
         for (int k = 0; k < np; k++) {
-            const size_t rows = k ? (size_t)a->out_h / 2 : (size_t)a->out_h;
-            const size_t w = k && !nv12 ? (size_t)a->out_w / 2 : (size_t)a->out_w;
+            const size_t rows = (size_t)d.plane_rows(k, a->out_h), w = (size_t)d.plane_row_bytes(k, a->out_w);
             const uintptr_t b = reinterpret_cast<uintptr_t>(planes[k]);
             ranges.push_back(PinRange{b, b + pitches[k] * (rows - 1) + w});
             r.p[k] = planes[k];
@@ -916,19 +878,19 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
         const bool in_conv = in_layout.converted();
         // the pieces' places in the packed buffer are the format's own: 4, 6 or 8 bytes per pixel of a piece's row;
         // a switch between them rebuilds the table
-        if (in_conv && a->conv_bpp != in_layout.run_bpp() && !a->runs.empty()) {
+        if (in_conv && a->conv_bpp != in_layout.run_bpp() && !a->native.runs.empty()) {
             size_t bytes = 0;
-            std::vector<ConvRun> t = run_table(in_layout, a->runs, a->in_w, bytes);
+            std::vector<FootRun> t = run_table(in_layout, a->native.runs, a->in_w, bytes);
             REQUIRE(bytes < ((size_t)1 << 32) && t.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
-            a->conv_table_dev.upload(t.data(), t.size());
+            a->conv.dev.upload(t.data(), t.size());
             for (auto& sl : a->slots)  // 4 to 8 bytes per pixel of a row pair against 3: larger packed buffers
                 if (sl.packed_host->n < bytes) {
                     sl.packed_host.reset(new PinnedBuf());
                     sl.packed_host->alloc(bytes);
                     sl.packed_dev.alloc(bytes);
                 }
-            a->conv_table = std::move(t);
-            a->conv_packed_bytes = bytes;
+            a->conv.runs = std::move(t);
+            a->conv.bytes = bytes;
             a->conv_bpp = in_layout.run_bpp();
         }
         // a pipeline with a converted input converts once for all its mappers, which read its NV12 frames
@@ -999,7 +961,7 @@ int octvr_async_info(const octvr_async* a, char* buf, size_t len) {
              "{\"mappers\": %d, \"inputs\": %d, \"packed_bytes\": %zu, \"runs\": %zu, \"input_frame_bytes\": %zu, "
              "\"output_bytes\": %zu, \"preview\": [%d, %d], \"flags\": %d, \"slots\": %d, \"pixel_formats\": [%d, %d], "
              "\"device_frames\": %lld, \"merge_launches\": %lld",
-             (int)a->mappers.size(), a->n_in, a->packed_bytes, a->runs.size(), in_bytes, out_bytes, a->preview_w,
+             (int)a->mappers.size(), a->n_in, a->native.bytes, a->native.runs.size(), in_bytes, out_bytes, a->preview_w,
              a->preview_h, a->flags, kSlots, a->in_fmt, a->out_fmt, (long long)a->device_frames,
              (long long)a->merge_launches.load());
     // per mapper the preview size it gathers from the source frames ([0, 0]: it previews from its result frame,

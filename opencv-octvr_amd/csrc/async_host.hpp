@@ -1,8 +1,9 @@
-// async_host.hpp — the AsyncMultiMapper pipeline's pure host arithmetic (no HIP, no device): the packing of
-// one footprint run from the caller's planes (async.cpp copy_in; debug_abi.cpp octvr_debug_pack_runs), the
-// merge of the output planes' byte ranges before they are page-locked (octvr_async_register_output), and the
-// region table and work-item arithmetic of the device-frame merge (octvr_async_push_device), which
-// merge_regions_kernel shares.
+// async_host.hpp — the AsyncMultiMapper pipeline's pure host arithmetic (no HIP, no device) on its output side:
+// the merge of the output planes' byte ranges before they are page-locked (octvr_async_register_output), where
+// the pieces of a region frame land in the output planes (region_pieces: the D2H copies, the copy-out and the
+// merge table all place them by it), and the region table and work-item arithmetic of the device-frame merge
+// (octvr_async_push_device), which merge_regions_kernel shares.  The input side (the layouts' planes, pack_run)
+// is frame_layout.hpp's.
 #pragma once
 
 #include <algorithm>
@@ -11,29 +12,9 @@
 #include <cstring>
 #include <vector>
 
+#include "frame_layout.hpp"
+
 namespace octvr {
-
-// Bytes of the luma part of one row of a run: groups [g0, g0 + ng) of 8 pixels, cut at the width.
-inline int run_luma_bytes(int w, int g0, int ng) { return std::min(8 * (g0 + ng), w) - 8 * g0; }
-
-// Packs the run (row pair rp, groups [g0, g0 + ng)) of a w-wide camera at d: luma row 2 rp, luma row
-// 2 rp + 1 (yb bytes each), then its chroma row — planar (nv12 == 0): cb bytes of U and cb of V, from
-// planes[1] / planes[2] at byte 4 g0; NV12: the yb bytes at byte 8 g0 of the U,V plane planes[1] (planes[2]
-// is not read).  w is even, so yb = 2 cb and both layouts pack 3 yb bytes.  Returns that size.
-inline size_t pack_run(uint8_t* d, int w, int rp, int g0, int ng, const uint8_t* const* planes, const size_t* pitches,
-                       int nv12) {
-    const int x0 = 8 * g0, yb = run_luma_bytes(w, g0, ng);
-    memcpy(d, planes[0] + (size_t)(2 * rp) * pitches[0] + x0, (size_t)yb);
-    memcpy(d + yb, planes[0] + (size_t)(2 * rp + 1) * pitches[0] + x0, (size_t)yb);
-    if (nv12) {
-        memcpy(d + 2 * yb, planes[1] + (size_t)rp * pitches[1] + x0, (size_t)yb);
-        return (size_t)(3 * yb);
-    }
-    const int c0 = 4 * g0, cb = std::max(0, std::min(4 * (g0 + ng), w / 2) - c0);
-    memcpy(d + 2 * yb, planes[1] + (size_t)rp * pitches[1] + c0, (size_t)cb);
-    memcpy(d + 2 * yb + cb, planes[2] + (size_t)rp * pitches[2] + c0, (size_t)cb);
-    return (size_t)(2 * yb + 2 * cb);
-}
 
 // A byte range [begin, end) of host memory.
 struct PinRange {
@@ -63,24 +44,43 @@ inline std::vector<PinRange> merge_pin_ranges(std::vector<PinRange> in, uintptr_
     return out;
 }
 
-// ---- the merge of the regions into one device frame (octvr_async_push_device, async_merge.hip) ----------
-// The functions below run on the host and, compiled by hipcc, in merge_regions_kernel: one definition of the
-// arithmetic, checked on the CPU (tests/cpp/async_merge_check.cpp).
-#ifdef __HIPCC__
-#define OCTVR_MERGE_HD __host__ __device__
-#else
-#define OCTVR_MERGE_HD
-#endif
-
+// ---- where a region lands ------------------------------------------------------------------------------------
 struct PlaneRect {  // a rectangle of a plane, in the plane's own pixels
     int x, y, w, h;
 };
 
-constexpr int kMergeMaxRegions = 32;  // regions of one merge launch (the table is a kernel argument)
-constexpr int kMergeChunk = 16;       // bytes of one work item's vector store
+// A mapper writes its region as a frame of its own, pitch = w: h rows of Y, then h / 2 chroma rows, each [U | V]
+// halves of w / 2 bytes (planar output) or w bytes of U,V pairs (NV12).  A piece of it is `rows` rows of `bytes`
+// bytes from byte `src` of that frame, which land at byte column x, row y of output plane `plane` (0: Y; 1: U,
+// or the U,V plane; 2: V).
+struct RegionPiece {
+    int plane;
+    size_t x, y, src, bytes, rows;
+};
+struct RegionPieces {
+    int n;  // 3, or 2 with NV12
+    RegionPiece p[3];  // the luma piece first; the chroma pieces have the same rows
+};
+// The pieces of the region with rectangle r in the Y plane and c in the U / V planes (c.w = r.w / 2 and
+// c.h = r.h / 2, octvr_async_create); in the U,V plane chroma column c.x is byte column 2 c.x.
+inline RegionPieces region_pieces(const PlaneRect& r, const PlaneRect& c, int nv12) {
+    const size_t w = (size_t)r.w, luma = (size_t)r.h * w, cw = (size_t)c.w, ch = (size_t)c.h;
+    RegionPieces o{nv12 ? 2 : 3, {{0, (size_t)r.x, (size_t)r.y, 0, w, (size_t)r.h}, {}, {}}};
+    if (nv12) {
+        o.p[1] = RegionPiece{1, 2 * (size_t)c.x, (size_t)c.y, luma, w, ch};
+    } else {
+        o.p[1] = RegionPiece{1, (size_t)c.x, (size_t)c.y, luma, cw, ch};
+        o.p[2] = RegionPiece{2, (size_t)c.x, (size_t)c.y, luma + w / 2, cw, ch};
+    }
+    return o;
+}
 
-// One region of the merged frame.  The source is the mapper's region frame, pitch = w: h rows of Y, then h / 2
-// chroma rows, each [U | V] halves of w / 2 bytes (planar output) or w bytes of U,V pairs (NV12).
+// ---- the merge of the regions into one device frame (octvr_async_push_device, async_merge.hip) ----------
+// merge_region_items and merge_item run on the host and, compiled by hipcc, in merge_regions_kernel: one
+// definition of the arithmetic, checked on the CPU (tests/cpp/async_merge_check.cpp).
+constexpr int kMergeMaxRegions = 32;  // regions of one merge launch (the table is a kernel argument)
+
+// One region of the merged frame; src is the mapper's region frame.
 struct MergeRegion {
     const uint8_t* src;
     int w, h;
@@ -96,15 +96,11 @@ struct MergeTable {
     MergeRegion r[kMergeMaxRegions];
 };
 
-// Work items of a row of n bytes: the bytes before the destination's first 16-byte boundary (item 0, at most
-// 15, possibly none), then 16-byte chunks, the last one possibly short.  An upper bound over every alignment.
-OCTVR_MERGE_HD inline uint32_t merge_row_items(int n) { return (uint32_t)((n + kMergeChunk - 1) / kMergeChunk + 1); }
-
-// Work items of a region, in order: h luma rows of merge_row_items(w); then per chroma row, NV12:
-// merge_row_items(w), planar: the U half's merge_row_items(w / 2), then the V half's.
-OCTVR_MERGE_HD inline uint64_t merge_region_items(int w, int h, int nv12) {
-    const uint64_t luma = (uint64_t)h * merge_row_items(w);
-    const uint64_t chroma = nv12 ? (uint64_t)(h / 2) * merge_row_items(w) : (uint64_t)(h / 2) * 2 * merge_row_items(w / 2);
+// Work items of a region (frame_layout.hpp row_chunk's), in order: h luma rows of row_items(w); then per chroma
+// row, NV12: row_items(w), planar: the U half's row_items(w / 2), then the V half's.
+OCTVR_LAYOUT_HD inline uint64_t merge_region_items(int w, int h, int nv12) {
+    const uint64_t luma = (uint64_t)h * row_items(w);
+    const uint64_t chroma = nv12 ? (uint64_t)(h / 2) * row_items(w) : (uint64_t)(h / 2) * 2 * row_items(w / 2);
     return luma + chroma;
 }
 
@@ -125,14 +121,17 @@ inline bool build_merge_table(const PlaneRect* r, const PlaneRect* c, const uint
             return false;
         if (b.x < 0 || b.y < 0 || b.w != a.w / 2 || b.h != a.h / 2 || b.x + b.w > out_w / 2 || b.y + b.h > out_h / 2)
             return false;
+        // the merged frame's planes: Y at its first byte, below it the U,V plane or U with V at byte out_w / 2
+        const size_t origin[3] = {0, (size_t)out_h * pitch, (size_t)out_h * pitch + (size_t)(out_w / 2)};
+        const RegionPieces pc = region_pieces(a, b, nv12);
+        auto off = [&](const RegionPiece& p) { return (uint32_t)(origin[p.plane] + p.y * pitch + p.x); };
         MergeRegion& m = t.r[k];
         m.src = src[k];
         m.w = a.w;
         m.h = a.h;
-        m.y_off = (uint32_t)((size_t)a.y * pitch + (size_t)a.x);
-        const size_t crow = (size_t)(out_h + b.y) * pitch;
-        m.u_off = (uint32_t)(crow + (nv12 ? 2 * (size_t)b.x : (size_t)b.x));
-        m.v_off = nv12 ? m.u_off : (uint32_t)(crow + (size_t)(out_w / 2) + (size_t)b.x);
+        m.y_off = off(pc.p[0]);
+        m.u_off = off(pc.p[1]);
+        m.v_off = off(pc.p[pc.n - 1]);
         m.first = (uint32_t)items;
         items += merge_region_items(a.w, a.h, t.nv12);
         if (items >= 0x7FFFFFFFull) return false;
@@ -150,13 +149,13 @@ struct MergeSpan {
     size_t dst;
     int len;
 };
-OCTVR_MERGE_HD inline MergeSpan merge_item(const MergeTable& t, uint32_t id, uintptr_t out_base) {
+OCTVR_LAYOUT_HD inline MergeSpan merge_item(const MergeTable& t, uint32_t id, uintptr_t out_base) {
     int k = 0;
     for (int i = 1; i < t.n; i++)
         if (id >= t.r[i].first) k = i;
     const MergeRegion m = t.r[k];
     uint32_t local = id - m.first;
-    const uint32_t per_luma = merge_row_items(m.w), luma = (uint32_t)m.h * per_luma;
+    const uint32_t per_luma = row_items(m.w), luma = (uint32_t)m.h * per_luma;
     const uint8_t* s;
     size_t d;
     int n;
@@ -176,7 +175,7 @@ OCTVR_MERGE_HD inline MergeSpan merge_item(const MergeTable& t, uint32_t id, uin
         n = m.w;
     } else {
         local -= luma;
-        const uint32_t per_half = merge_row_items(m.w / 2);
+        const uint32_t per_half = row_items(m.w / 2);
         const uint32_t half_row = local / per_half;  // 2 * chroma row + (0: U, 1: V)
         chunk = local - half_row * per_half;
         const uint32_t row = half_row >> 1, v = half_row & 1u;
@@ -184,12 +183,10 @@ OCTVR_MERGE_HD inline MergeSpan merge_item(const MergeTable& t, uint32_t id, uin
         d = (size_t)(v ? m.v_off : m.u_off) + (size_t)row * t.pitch;
         n = m.w / 2;
     }
-    const int head = (int)((0 - (out_base + d)) & (uintptr_t)(kMergeChunk - 1));
-    const int h = head < n ? head : n;
-    if (chunk == 0) return MergeSpan{s, d, h};
-    const int b0 = h + kMergeChunk * (int)(chunk - 1);
-    if (b0 >= n) return MergeSpan{s, d, 0};
-    return MergeSpan{s + b0, d + (size_t)b0, n - b0 < kMergeChunk ? n - b0 : kMergeChunk};
+    const RowChunk c = row_chunk(out_base + d, n, (int)chunk);
+    if (chunk == 0) return MergeSpan{s, d, c.head};
+    if (c.b0 >= n) return MergeSpan{s, d, 0};
+    return MergeSpan{s + c.b0, d + (size_t)c.b0, c.len(n)};
 }
 
 }  // namespace octvr

@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(256) merge_regions_kernel(uint8_t* __restrict_
     if (id >= t.items) return;
     const MergeSpan sp = merge_item(t, id, reinterpret_cast<uintptr_t>(out));
     uint8_t* const d = out + sp.dst;
-    if (sp.len == kMergeChunk) {
+    if (sp.len == kChunk) {
         *reinterpret_cast<uint4*>(d) = load16(sp.src);
         return;
     }

@@ -26,23 +26,11 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
         REQUIRE(n_inputs > 0 && n_inputs <= kMaxCams && n_runs >= 0, "bad counts");
         REQUIRE(format == OCTVR_PIX_YUV420P || format == OCTVR_PIX_NV12 || converted_format(format),
                 "pixel format must be an OCTVR_PIX_* value");
-        const bool nv12 = format == OCTVR_PIX_NV12;
         const LayoutDesc d = layout_of(format);
         for (int i = 0; i < n_inputs; i++) {
-            const size_t w = (size_t)in_w[i];
             REQUIRE(in_w[i] > 0 && in_h[i] > 0 && in_w[i] % 2 == 0 && in_h[i] % 2 == 0, "input sizes must be even");
-            if (d.converted()) {  // one packed plane; Y and a U,V plane; or Y, U and V with half a row's bytes each
-                const size_t rb = (size_t)d.row_bytes(in_w[i]);
-                auto plane = [&](int k, size_t bytes) { return planes[3 * i + k] && pitches[3 * i + k] >= bytes; };
-                REQUIRE(plane(0, rb) && (d.packed() || (d.halves() ? plane(1, rb / 2) && plane(2, rb / 2) : plane(1, rb))),
-                        "bad input plane");
-                continue;
-            }
-            REQUIRE(planes[3 * i] && planes[3 * i + 1] && pitches[3 * i] >= w, "bad input plane");
-            if (nv12)
-                REQUIRE(pitches[3 * i + 1] >= w, "bad input plane");
-            else
-                REQUIRE(planes[3 * i + 2] && pitches[3 * i + 1] >= w / 2 && pitches[3 * i + 2] >= w / 2, "bad input plane");
+            for (int k = 0; k < d.planes(); k++)
+                REQUIRE(planes[3 * i + k] && pitches[3 * i + k] >= (size_t)d.plane_row_bytes(k, in_w[i]), "bad input plane");
         }
         size_t off = 0;
         for (int k = 0; k < n_runs; k++) {
@@ -51,11 +39,9 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
             const int w = in_w[cam], h = in_h[cam];
             REQUIRE(rp < (uint32_t)h / 2 && ng > 0 && g0 < (uint32_t)(w + 7) / 8 && ng <= (uint32_t)(w + 7) / 8 - g0,
                     "run outside its frame");
-            const size_t n = (size_t)(d.converted() ? d.run_bpp() : 3) * (size_t)run_luma_bytes(w, (int)g0, (int)ng);
+            const size_t n = (size_t)d.run_bpp() * (size_t)run_px(w, (int)g0, (int)ng);
             REQUIRE(off + n <= cap, "buffer too small");
-            const size_t got = d.converted()
-                                   ? pack_run(d, packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam)
-                                   : pack_run(packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam, nv12);
+            const size_t got = pack_run(d, packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam);
             REQUIRE(got == n, "pack_run size");
             if (sizes) sizes[k] = got;
             off += got;

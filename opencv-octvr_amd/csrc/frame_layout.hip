@@ -91,12 +91,12 @@ constexpr uint32_t kUnpackLanes = 16;  // lanes of one table piece
 }  // namespace
 
 template <class L>
-__global__ void __launch_bounds__(256) layout_unpack_kernel(const ConvRun* __restrict__ table, int n_pieces, ConvSources src,
+__global__ void __launch_bounds__(256) layout_unpack_kernel(const FootRun* __restrict__ table, int n_pieces, ConvSources src,
                                                             FootFrames fr) {
     constexpr LayoutDesc d = L::desc;
     const int piece = (int)(blockIdx.x * (256u / kUnpackLanes) + threadIdx.x / kUnpackLanes);
     if (piece >= n_pieces) return;
-    const ConvRun r = table[piece];
+    const FootRun r = table[piece];
     const int cam = (int)(r.cam & 31u);
     const int w = fr.w[cam], h = fr.h[cam];
     const uint8_t* const s = src.packed ? src.packed : src.f[cam];
@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(256) layout_pack_kernel(const uint8_t* __restr
     pack_lane<L>(PackMem{}, src, out, w, h, pack_item(d, w, h, pitch, reinterpret_cast<uintptr_t>(out), id));
 }
 
-hipError_t launch_layout_unpack(int pix, const ConvRun* table, int n_pieces, const ConvSources& src, const FootFrames& frames,
+hipError_t launch_layout_unpack(int pix, const FootRun* table, int n_pieces, const ConvSources& src, const FootFrames& frames,
                                 hipStream_t s) {
     if (!converted_format(pix)) return hipErrorInvalidValue;
     if (n_pieces <= 0) return hipSuccess;

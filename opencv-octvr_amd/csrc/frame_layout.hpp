@@ -1,7 +1,8 @@
-// frame_layout.hpp — the arithmetic of the capture layouts the Mapper and the pipeline convert to and from their
-// internal 8-bit NV12 frames (the eight OCTVR_PIX_* values >= 16): which bytes a work item of
-// layout_unpack_kernel / layout_pack_kernel (frame_layout.hip) loads and which it stores, the packing of a
-// footprint run of such planes (async.cpp copy_in) and the split of footprint runs into the unpack kernel's table.
+// frame_layout.hpp — the arithmetic of the frame layouts (the ten OCTVR_PIX_* values): the planes of a frame and the
+// packing of a footprint run from them (async.cpp copy_in), for every layout; and for the eight capture layouts the
+// Mapper and the pipeline convert to and from their internal 8-bit NV12 frames (the values >= 16) which bytes a work
+// item of layout_unpack_kernel / layout_pack_kernel (frame_layout.hip) loads and which it stores, and the split of
+// footprint runs into the unpack kernel's table.
 // No HIP types: the lane bodies are templates over a layout descriptor and a memory policy, so the kernels
 // (non-temporal / vector accesses) and tests/cpp/frame_layout_check.cpp (memcpy against exactly sized heap blocks)
 // execute one definition.
@@ -18,6 +19,8 @@
 //   chroma_rows  chroma rows per row pair: 1 (4:2:0) or 2 (4:2:2).
 //
 //                       bytes  msb  chroma  luma_odd  chroma_rows   row bytes  rows     packed B / pixel of a run
+//   YUV420P               1     -   halves     -          1             w      3 h / 2        3
+//   NV12                  1     -   pairs      -          1             w      3 h / 2        3
 //   UYVY422               1     -   packed    yes         2           2 w      h              4
 //   YUYV422               1     -   packed    no          2           2 w      h              4
 //   YUV422P               1     -   halves     -          2             w      2 h            4
@@ -26,6 +29,9 @@
 //   YUV420P10             2    no   halves     -          1           2 w      3 h / 2        6
 //   P210                  2    yes  pairs      -          2           2 w      2 h            8
 //   YUV422P10             2    no   halves     -          2           2 w      2 h            8
+// YUV420P and NV12 are native: the kernels read and write them in place, nothing converts them (converted() is
+// false, with_layout has no case for them).  On the host a frame is planes() planes, as octvr_async_push takes
+// them: the packed kind one plane; pairs Y and the U,V plane; halves Y, U and V, each half a row's bytes wide.
 //
 // The 8-bit side of both conversions is NV12 at pitch = width ("Y over U,V pairs": h rows of Y, h / 2 rows of
 // U,V pairs), so the 8-pixel group g of row pair r is luma bytes [8 g, 8 g + 8) of rows 2r, 2r + 1 and chroma
@@ -51,17 +57,22 @@ namespace octvr {
 // ---- the layouts ---------------------------------------------------------------------------------------------
 enum ChromaKind : int { kChromaPacked = 0, kChromaPairs = 1, kChromaHalves = 2 };
 struct LayoutDesc {
-    int bytes;        // 0: not a converted format
+    int bytes;        // 0: no OCTVR_PIX_* value
     bool msb;
     int chroma;
     bool luma_odd;
     int chroma_rows;
-    OCTVR_LAYOUT_HD constexpr bool converted() const { return bytes != 0; }
+    bool native = false;  // YUV420P, NV12
+    OCTVR_LAYOUT_HD constexpr bool converted() const { return bytes != 0 && !native; }
     OCTVR_LAYOUT_HD constexpr bool packed() const { return chroma == kChromaPacked; }
     OCTVR_LAYOUT_HD constexpr bool halves() const { return chroma == kChromaHalves; }
     // bytes per row and rows of a w x h frame
     OCTVR_LAYOUT_HD constexpr int row_bytes(int w) const { return (packed() ? 2 : 1) * bytes * w; }
     OCTVR_LAYOUT_HD constexpr int rows(int h) const { return packed() ? h : h + chroma_rows * (h / 2); }
+    // the host planes of such a frame, and bytes per row and rows of plane k
+    constexpr int planes() const { return packed() ? 1 : halves() ? 3 : 2; }
+    constexpr int plane_row_bytes(int k, int w) const { return k && halves() ? row_bytes(w) / 2 : row_bytes(w); }
+    constexpr int plane_rows(int k, int h) const { return k ? chroma_rows * (h / 2) : h; }
     // packed bytes per pixel of a table piece's row: its two luma rows and its chroma row(s) (pack_run)
     OCTVR_LAYOUT_HD constexpr int run_bpp() const { return packed() ? 4 : bytes * (2 + chroma_rows); }
     // a frame of 16-bit words has an even base and an even pitch (a sample's natural alignment)
@@ -98,13 +109,44 @@ inline bool with_layout(int pix, F&& f) {
     }
     return false;
 }
-// The run-time lookup; layout_of(pix).converted() is false for every other format.
+// The run-time lookup of all ten layouts; bytes == 0 for any other value.
 inline LayoutDesc layout_of(int pix) {
+    if (pix == 0) return LayoutDesc{1, false, kChromaHalves, false, 1, true};  // OCTVR_PIX_YUV420P
+    if (pix == 1) return LayoutDesc{1, false, kChromaPairs, false, 1, true};   // OCTVR_PIX_NV12
     LayoutDesc d{0, false, 0, false, 0};
     with_layout(pix, [&](auto tag) { d = decltype(tag)::desc; });
     return d;
 }
 inline bool converted_format(int pix) { return layout_of(pix).converted(); }
+
+// Why (base, pitch) is no whole w x h device frame of the layout below `limit` bytes (what the kernels that touch
+// it address with 32 bits); NULL when it is one.
+inline const char* frame_fault(const LayoutDesc& d, const void* base, size_t pitch, int w, int h, uint64_t limit) {
+    if (!base) return "frame is NULL";
+    if (!d.aligned(base, pitch)) return "frame address and pitch must be multiples of 2 for 16-bit samples";
+    if (pitch < (size_t)d.row_bytes(w)) return "pitch smaller than a row of the format";
+    if ((uint64_t)pitch * (uint64_t)d.rows(h) >= limit) return "frame larger than 2 GiB";
+    return nullptr;
+}
+
+// ---- rows in 16-byte chunks ----------------------------------------------------------------------------------
+// The copy kernels (layout_pack_kernel, merge_regions_kernel) cut a destination row of n bytes whose first byte is
+// at address a into work items: item 0 is the bytes before the row's first 16-byte boundary (at most 15, possibly
+// none), then 16-byte chunks, the last one possibly short.  row_items: an upper bound over every alignment.
+// row_chunk: item 0 is `head` bytes from byte 0; item `chunk` > 0 is len(n) bytes from byte b0, nothing when b0 >= n.
+// len = 16 only at a 16-byte aligned address.  The caller branches on the three cases itself: its work item differs
+// per case, and the kernels keep the code they had.
+constexpr int kChunk = 16;
+OCTVR_LAYOUT_HD inline uint32_t row_items(int n) { return (uint32_t)((n + kChunk - 1) / kChunk + 1); }
+struct RowChunk {
+    int head, b0;
+    OCTVR_LAYOUT_HD int len(int n) const { return n - b0 < kChunk ? n - b0 : kChunk; }
+};
+OCTVR_LAYOUT_HD inline RowChunk row_chunk(uintptr_t a, int n, int chunk) {
+    const int to_boundary = (int)((0 - a) & (uintptr_t)(kChunk - 1));
+    const int head = to_boundary < n ? to_boundary : n;
+    return RowChunk{head, head + kChunk * (chunk - 1)};
+}
 
 // ---- bytes ---------------------------------------------------------------------------------------------------
 struct Words4 {
@@ -205,16 +247,19 @@ OCTVR_LAYOUT_HD inline uint32_t widen_alternate(uint32_t a, int odd) {
 }
 
 // ---- in: the unpack kernel's table and work items ------------------------------------------------------------
-// A run is ng consecutive 8-pixel groups from group g0 of row pair rp of camera cam (kernels.hpp FootRun, the
-// same four words).  The source is either the caller's frame (src_pitch >= the layout's row bytes) or the
-// pipeline's packed upload buffer (src_pitch == 0: the run's bytes at `off`, pack_run's layout).
-struct ConvRun {
+// A run is ng consecutive 8-pixel groups from group g0 of row pair rp of camera cam (host_common.hpp
+// SourceFootprint), the entry of every upload table: the native layouts' (mapper.cpp footprint_runs;
+// unpack_runs_kernel, unpack_runs_nv12_kernel) and the converted layouts' (run_table below).  The source of an
+// unpack is either the caller's frame (src_pitch >= the layout's row bytes) or the pipeline's packed upload buffer
+// (src_pitch == 0: the run's bytes at `off`, pack_run's layout).
+struct FootRun {
     uint32_t cam;  // camera | row pair << 8
     uint32_t g0, ng;
     uint32_t off;
 };
+using ConvRun = FootRun;  // a piece of run_table: a run of at most kWave groups
 
-// Luma samples of one row of the run: its groups cut at the width (async_host.hpp run_luma_bytes).
+// Luma samples of one row of the run: its groups cut at the width.
 OCTVR_LAYOUT_HD inline int run_px(int w, int g0, int ng) { return (8 * (g0 + ng) < w ? 8 * (g0 + ng) : w) - 8 * g0; }
 
 // What the lane of group k (< r.ng) of table piece r does for a w x h camera.  It writes px bytes at y0, at y1 and
@@ -231,7 +276,7 @@ struct LayoutItem {
     size_t sy0, sy1, su0, su1, sv0, sv1;
     size_t y0, y1, c;
 };
-OCTVR_LAYOUT_HD inline LayoutItem unpack_item(const LayoutDesc& d, int w, int h, size_t src_pitch, const ConvRun& r, int k) {
+OCTVR_LAYOUT_HD inline LayoutItem unpack_item(const LayoutDesc& d, int w, int h, size_t src_pitch, const FootRun& r, int k) {
     const int rp = (int)(r.cam >> 8), g = (int)r.g0 + k;
     const size_t S = (size_t)d.bytes;
     LayoutItem it;
@@ -343,10 +388,11 @@ OCTVR_LAYOUT_HD inline void unpack_lane(const Mem& mem, const uint8_t* src, uint
     mem.store8(dst + it.c, c);
 }
 
-// Packs piece (row pair rp, groups [g0, g0 + ng)) of a w-wide camera at d from host planes laid out as
+// Packs run (row pair rp, groups [g0, g0 + ng)) of a w-wide camera at d from host planes laid out as
 // octvr_async_push's: the packed kind planes[0]; pairs planes[0] = Y, planes[1] = U,V pairs; halves
-// planes[0 / 1 / 2] = Y, U, V.  The layout the packed-source items above read; returns its size, run_bpp() bytes
-// per pixel of the piece's row.
+// planes[0 / 1 / 2] = Y, U, V.  Any of the ten layouts: what the packed-source items above read, and for the native
+// two what unpack_runs_kernel / unpack_runs_nv12_kernel read (w is even, so the U and the V part are half the pair
+// row each and both pack 3 bytes per pixel).  Returns its size, run_bpp() bytes per pixel of the run's row.
 inline size_t pack_run(const LayoutDesc& l, uint8_t* d, int w, int rp, int g0, int ng, const uint8_t* const* planes,
                        const size_t* pitches) {
     const size_t S = (size_t)l.bytes, n = (size_t)run_px(w, g0, ng), G = (size_t)g0;
@@ -371,15 +417,15 @@ inline size_t pack_run(const LayoutDesc& l, uint8_t* d, int w, int rp, int g0, i
 // frame's unpack reads.
 constexpr int kWave = 64;
 template <class Run>
-inline std::vector<ConvRun> run_table(const LayoutDesc& l, const std::vector<Run>& runs, const std::vector<int>& in_w,
+inline std::vector<FootRun> run_table(const LayoutDesc& l, const std::vector<Run>& runs, const std::vector<int>& in_w,
                                       size_t& bytes) {
-    std::vector<ConvRun> t;
+    std::vector<FootRun> t;
     bytes = 0;
     for (const Run& r : runs) {
         const int w = in_w[r.cam & 31u];
         for (uint32_t k = 0; k < r.ng; k += kWave) {
             const uint32_t ng = r.ng - k < (uint32_t)kWave ? r.ng - k : (uint32_t)kWave;
-            t.push_back(ConvRun{r.cam, r.g0 + k, ng, (uint32_t)bytes});
+            t.push_back(FootRun{r.cam, r.g0 + k, ng, (uint32_t)bytes});
             bytes += (size_t)l.run_bpp() * (size_t)run_px(w, (int)(r.g0 + k), (int)ng);
         }
     }
@@ -387,16 +433,12 @@ inline std::vector<ConvRun> run_table(const LayoutDesc& l, const std::vector<Run
 }
 
 // ---- out: the pack kernel's work items -----------------------------------------------------------------------
-// The destination is a list of rows, each with its own head / chunk / tail arithmetic, as the device-frame
-// merge's (async_host.hpp merge_item): item 0 of a row is the bytes before the row's first 16-byte boundary (at
-// most 15, possibly none), then 16-byte chunks, the last one possibly short (all even for 16-bit samples, as the
-// base, the pitch and a half row's start are):
+// The destination is a list of rows, each cut into row_chunk's items (all even for 16-bit samples, as the base,
+// the pitch and a half row's start are):
 //   packed   h rows of 2 w bytes;
 //   pairs    rows(h) rows of S w bytes: luma rows, then chroma rows;
 //   halves   h luma rows of S w bytes, then half rows of S w / 2 bytes, two per chroma row: half row q is the U
 //            (q even) or V (q odd) half of chroma row q >> 1, at byte (q & 1) S w / 2 of frame row h + (q >> 1).
-constexpr int kChunk = 16;
-OCTVR_LAYOUT_HD inline uint32_t row_items(int n) { return (uint32_t)((n + kChunk - 1) / kChunk + 1); }
 OCTVR_LAYOUT_HD inline int full_rows(const LayoutDesc& d, int h) { return d.halves() ? h : d.rows(h); }
 OCTVR_LAYOUT_HD inline int half_rows(const LayoutDesc& d, int h) { return d.halves() ? 2 * d.chroma_rows * (h / 2) : 0; }
 OCTVR_LAYOUT_HD inline uint64_t pack_items(const LayoutDesc& d, int w, int h) {
@@ -429,17 +471,15 @@ OCTVR_LAYOUT_HD inline LayoutSpan pack_item(const LayoutDesc& d, int w, int h, s
         sp.n = n_full / 2;
         sp.dst = (size_t)(h + (int)(q >> 1)) * pitch + (size_t)((q & 1u) ? n_full / 2 : 0);
     }
-    const int head = (int)((0 - (out_base + sp.dst)) & (uintptr_t)(kChunk - 1));
-    const int hd = head < sp.n ? head : sp.n;
+    const RowChunk c = row_chunk(out_base + sp.dst, sp.n, chunk);
     if (chunk == 0) {
-        sp.len = hd;
+        sp.len = c.head;
         return sp;
     }
-    const int b0 = hd + kChunk * (chunk - 1);
-    if (b0 >= sp.n) return sp;
-    sp.b0 = b0;
-    sp.len = sp.n - b0 < kChunk ? sp.n - b0 : kChunk;
-    sp.dst += (size_t)b0;
+    if (c.b0 >= sp.n) return sp;
+    sp.b0 = c.b0;
+    sp.len = c.len(sp.n);
+    sp.dst += (size_t)c.b0;
     return sp;
 }
 

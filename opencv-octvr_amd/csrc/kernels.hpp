@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "camera_math.hpp"
+#include "frame_layout.hpp"
 #include "multiband_plan.hpp"
 
 namespace octvr {
@@ -271,14 +272,9 @@ hipError_t launch_set_gains(const double* host_gains, int n, double* gains_dev, 
 hipError_t launch_gain_solve(const double* A, const double* b, int n, int count, bool lean, double* x, int* ok,
                              hipStream_t s);
 
-// AsyncMultiMapper footprint upload (async.cpp): a run is `ng` consecutive 8-pixel groups from group g0 of
-// row pair r of camera `cam` (host_common.hpp SourceFootprint), packed at `off` as luma row 2r, luma row
-// 2r + 1, then its chroma row of U and of V; the frames are "Y over [U | V]" with pitch = width.
-struct FootRun {
-    uint32_t cam;  // camera | row pair << 8
-    uint32_t g0, ng;
-    uint32_t off;
-};
+// AsyncMultiMapper footprint upload (async.cpp): the runs of a table (frame_layout.hpp FootRun), each packed at its
+// `off` by pack_run, into the cameras' device frames (pitch = width).  launch_unpack_runs: luma row 2r, luma row
+// 2r + 1, then the chroma row's U and V parts, into frames "Y over [U | V]".
 struct FootFrames {
     uint8_t* f[kMaxCams];
     int w[kMaxCams], h[kMaxCams];
@@ -296,17 +292,16 @@ struct MergeTable;
 hipError_t launch_merge_regions(uint8_t* out, const MergeTable& t, hipStream_t s);
 // The converted capture layouts (the OCTVR_PIX_* values >= 16, frame_layout.hip; the arithmetic, the table and the
 // layouts' descriptors in frame_layout.hpp; `pix` is the OCTVR_PIX_* value).
-// launch_layout_unpack: the groups of the table's pieces from sources of the layout into the cameras' NV12 frames
-// `frames` (pitch = width).  The sources are the pipeline's packed upload buffer (`packed`, pack_run's pieces, each
-// at its `off` of run_table) or, with packed NULL, one whole frame of the layout per camera at its pitch (>= the
-// layout's row bytes; base and pitch even for 16-bit samples).
-struct ConvRun;
+// launch_layout_unpack: the groups of the table's pieces (run_table: runs of at most 64 groups) from sources of the
+// layout into the cameras' NV12 frames `frames` (pitch = width).  The sources are the pipeline's packed upload
+// buffer (`packed`, each piece at its `off`) or, with packed NULL, one whole frame of the layout per camera at its
+// pitch (>= the layout's row bytes; base and pitch even for 16-bit samples).
 struct ConvSources {
     const uint8_t* packed;
     const uint8_t* f[kMaxCams];
     size_t pitch[kMaxCams];
 };
-hipError_t launch_layout_unpack(int pix, const ConvRun* table, int n_pieces, const ConvSources& src, const FootFrames& frames,
+hipError_t launch_layout_unpack(int pix, const FootRun* table, int n_pieces, const ConvSources& src, const FootFrames& frames,
                                 hipStream_t s);
 // launch_layout_pack: the whole w x h NV12 frame `src` (pitch = w) into the frame `out` of the layout at `pitch`
 // (>= the layout's row bytes, any alignment; even base and pitch for 16-bit samples); bytes of a row past the

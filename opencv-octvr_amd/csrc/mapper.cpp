@@ -84,17 +84,13 @@ void setup_overlays(octvr_mapper& m, const Camera& camera) {
     m.ov.view = OverlayList{m.ov.groups.p, m.ov.entries.p, (int)b.groups.size()};
 }
 
-void check_out_pitch(const octvr_mapper* m, size_t out_pitch) {
-    if (m->conv_out) {  // a whole frame of the layout; the stitch writes the slot's own NV12 frame
-        const LayoutDesc d = layout_of(m->conv_fmt_out);
-        REQUIRE(out_pitch >= (size_t)d.row_bytes(m->SW), "output pitch smaller than a row of the format");
-        REQUIRE(d.aligned(nullptr, out_pitch), "10-bit output pitch must be a multiple of 2");
-        REQUIRE((uint64_t)out_pitch * (uint64_t)d.rows(m->SH) < 0x7FFFFF80ull, "output frame larger than 2 GiB");
-        return;
-    }
-    REQUIRE(out_pitch >= (size_t)m->SW, "output pitch smaller than width");
-    // the stitch kernel addresses the output through a buffer resource with 32-bit offsets
-    REQUIRE((uint64_t)out_pitch * (m->SH + m->SH / 2) < 0x7FFFFF80ull, "output frame larger than 2 GiB");
+// The caller's output frame: a whole frame of the converted layout (the stitch then writes the slot's own NV12
+// frame), else of either 4:2:0 layout, which the stitch kernel addresses through a buffer resource with 32-bit
+// offsets.
+void check_out_frame(const octvr_mapper* m, const uint8_t* out_dev, size_t out_pitch) {
+    const LayoutDesc d = layout_of(m->conv_out ? m->conv_fmt_out : OCTVR_PIX_YUV420P);
+    const char* why = frame_fault(d, out_dev, out_pitch, m->SW, m->SH, 0x7FFFFF80ull);
+    REQUIRE(!why, std::string("output ") + why);
 }
 
 // The kernels' view of one frame's inputs.
@@ -111,10 +107,8 @@ ConvSources conv_sources(const octvr_mapper* m, const uint8_t* const* in_dev, co
     memset(&cs, 0, sizeof cs);
     const LayoutDesc d = layout_of(m->conv_fmt_in);
     for (int i = 0; i < m->nc; i++) {
-        REQUIRE(in_dev[i], "bad input frame");
-        REQUIRE(in_pitch[i] >= (size_t)d.row_bytes(m->in_w[i]), "input pitch smaller than a row of the format");
-        REQUIRE(d.aligned(in_dev[i], in_pitch[i]), "10-bit input frames and pitches must be multiples of 2");
-        REQUIRE((uint64_t)in_pitch[i] * (uint64_t)d.rows(m->in_h[i]) < 0x7FFFFFFFull, "input frame larger than 2 GiB");
+        const char* why = frame_fault(d, in_dev[i], in_pitch[i], m->in_w[i], m->in_h[i], 0x7FFFFFFFull);
+        REQUIRE(!why, std::string("input ") + why);
         cs.f[i] = in_dev[i];
         cs.pitch[i] = in_pitch[i];
     }
@@ -326,7 +320,7 @@ void mapper_set_conv(octvr_mapper* m, int in_fmt, int out_fmt) {
         m->conv_foot_runs = runs;
         // the pieces are the same in every layout; the offsets (4 bytes per pixel here) are not read
         size_t bytes4 = 0;
-        const std::vector<ConvRun> table = run_table(LayoutUyvy::desc, runs, m->in_w, bytes4);
+        const std::vector<FootRun> table = run_table(LayoutUyvy::desc, runs, m->in_w, bytes4);
         REQUIRE(bytes4 < ((size_t)1 << 32) && table.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
         m->conv_in_px = bytes4 / 4;
         m->conv_runs = runs.size();
@@ -356,8 +350,7 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
             ensure_result(*m);
         }
     }
-    check_out_pitch(m, out_pitch);
-    REQUIRE(!m->conv_out || layout_of(m->conv_fmt_out).aligned(out_dev, 0), "10-bit output frame must be 2-byte aligned");
+    check_out_frame(m, out_dev, out_pitch);
     DeviceGuard dg(m->device);
     // converted sides: the slot's unpack launch fills its NV12 input frames, which every stage below reads,
     // and the stitch writes the slot's NV12 output frame, which the pack launch converts at the end
@@ -437,9 +430,7 @@ void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, 
     }
     REQUIRE((int)m->slots.size() >= nb, "a batch of n frames needs n frames in flight (octvr_mapper_set_frames_in_flight)");
     REQUIRE(nb <= 2 || m->nc <= 16, "a batch of 4 frames holds 16 cameras per frame (inputs and overlays)");
-    check_out_pitch(m, out_pitch);
-    for (int f = 0; f < nb; f++)
-        REQUIRE(!m->conv_out || layout_of(m->conv_fmt_out).aligned(out_dev[f], 0), "10-bit output frame must be 2-byte aligned");
+    for (int f = 0; f < nb; f++) check_out_frame(m, out_dev[f], out_pitch);
     DeviceGuard dg(m->device);
     FrameSet fs[kMaxBatch];  // every frame checked before any of them puts work on the stream
     ConvSources us[kMaxBatch];

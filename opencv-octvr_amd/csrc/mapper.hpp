@@ -90,7 +90,7 @@ struct octvr_mapper {
     // read); conv_in_px: the pixels of the pieces' rows, run_bpp() packed bytes each.
     bool conv_in = false, conv_out = false;
     int conv_fmt_in = 0, conv_fmt_out = 0;
-    DevBuf<octvr::ConvRun> conv_table;
+    DevBuf<octvr::FootRun> conv_table;
     size_t conv_runs = 0, conv_in_px = 0;
     std::vector<octvr::FootRun> conv_foot_runs;  // the runs the table was cut from (octvr_debug_mapper_uyvy_runs)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events, free_events;  // recorded / reusable

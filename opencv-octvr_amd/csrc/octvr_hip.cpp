@@ -520,7 +520,7 @@ int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
                         {"yuv422", [](int pix, const LayoutDesc& d) { return d.bytes == 1 && pix != OCTVR_PIX_UYVY422; }},
                         {"yuv10", [](int, const LayoutDesc& d) { return d.bytes == 2; }}};
         for (const auto& f : families) {
-            const bool i = f.is(m->conv_fmt_in, li), o = f.is(m->conv_fmt_out, lo);
+            const bool i = m->conv_in && f.is(m->conv_fmt_in, li), o = m->conv_out && f.is(m->conv_fmt_out, lo);
             js += std::string(", \"") + f.prefix + "_runs\": " + std::to_string(i ? m->conv_runs : 0) + ", \"" + f.prefix +
                   "_in_bytes\": " + std::to_string(i ? m->conv_in_px * (size_t)li.run_bpp() : 0) + ", \"" + f.prefix +
                   "_out_bytes\": " + std::to_string(o ? (size_t)lo.row_bytes(m->SW) * (size_t)lo.rows(m->SH) : 0);

@@ -10,6 +10,11 @@
 //     pattern of the edge values through the two-samples-per-dword narrowing; widening and back.
 //   check_descriptors: layout_of against the formats' row bytes, rows and packed bytes per pixel; the values that
 //     are no converted format.
+//   check_planes: for all ten layouts (the two native 4:2:0 ones included) the frame's row bytes, rows and packed
+//     bytes per pixel and each host plane's row bytes and rows against the table of the header's comment, written
+//     out here in numbers; frame_fault's four refusals at each call's own limit.
+//   check_row_chunks: rows of 0, 1, 15, 16, 17, 31 and 33 bytes at all 16 alignments: the items tile the row exactly
+//     once, in order, and a full 16-byte item is 16-byte aligned; items past the row's last are empty.
 //   check_unpack, for each layout: widths 8k, 8k + 2, 8k + 4, 8k + 6 and 328, 330, 332; pitches minimal and
 //     minimal + 6; every alignment of the source base within 16 (every even one for 16-bit samples) and both
 //     source kinds (the caller's frame, the packed upload buffer); an NV12 frame at an 8-byte aligned and at a 2
@@ -242,6 +247,80 @@ void check_samples() {
     CHECK(rule8(3) == 1 && rule8(6) == 2 && ((rule8(3) + rule8(6) + 1) >> 1) == 2, "the rule's own example");
 }
 
+// The header comment's table for a 16 x 4 picture, in numbers, and per host plane (Y / packed; U or U,V; V) its
+// row bytes and rows: -1 = no such plane.
+void check_planes() {
+    const struct {
+        int pix, row_bytes, rows, run_bpp, planes;
+        int plane_bytes[3], plane_rows[3];
+    } T[10] = {
+        {0, 16, 6, 3, 3, {16, 8, 8}, {4, 2, 2}},     // YUV420P
+        {1, 16, 6, 3, 2, {16, 16, -1}, {4, 2, -1}},  // NV12
+        {16, 32, 4, 4, 1, {32, -1, -1}, {4, -1, -1}},  // UYVY422
+        {17, 32, 4, 4, 1, {32, -1, -1}, {4, -1, -1}},  // YUYV422
+        {18, 16, 8, 4, 3, {16, 8, 8}, {4, 4, 4}},      // YUV422P
+        {19, 16, 8, 4, 2, {16, 16, -1}, {4, 4, -1}},   // NV16
+        {32, 32, 6, 6, 2, {32, 32, -1}, {4, 2, -1}},   // P010
+        {33, 32, 6, 6, 3, {32, 16, 16}, {4, 2, 2}},    // YUV420P10
+        {34, 32, 8, 8, 2, {32, 32, -1}, {4, 4, -1}},   // P210
+        {35, 32, 8, 8, 3, {32, 16, 16}, {4, 4, 4}},    // YUV422P10
+    };
+    for (const auto& t : T) {
+        const LayoutDesc d = layout_of(t.pix);
+        CHECK(d.bytes != 0 && d.native == (t.pix < 2) && d.converted() == (t.pix >= 16) && converted_format(t.pix) == (t.pix >= 16),
+              "%d: native / converted", t.pix);
+        CHECK(d.row_bytes(16) == t.row_bytes && d.rows(4) == t.rows && d.run_bpp() == t.run_bpp, "%d: frame %d x %d, %d B / pixel",
+              t.pix, d.row_bytes(16), d.rows(4), d.run_bpp());
+        CHECK(d.planes() == t.planes, "%d: %d planes", t.pix, d.planes());
+        int frame_rows = 0;
+        for (int k = 0; k < t.planes; k++) {
+            CHECK(d.plane_row_bytes(k, 16) == t.plane_bytes[k] && d.plane_rows(k, 4) == t.plane_rows[k], "%d: plane %d is %d x %d", t.pix, k,
+                  d.plane_row_bytes(k, 16), d.plane_rows(k, 4));
+            frame_rows += k < 2 ? d.plane_rows(k, 4) : 0;  // V lies beside U in the frame's chroma rows
+        }
+        CHECK(frame_rows == t.rows, "%d: the planes' rows are the frame's", t.pix);
+        // frame_fault: the limit is the caller's, the first byte count refused
+        uint8_t* const even = reinterpret_cast<uint8_t*>(uintptr_t(0x1000));
+        const size_t rb = (size_t)t.row_bytes;
+        CHECK(frame_fault(d, even, rb, 16, 4, rb * t.rows + 1) == nullptr, "%d: a frame at its minimal pitch", t.pix);
+        CHECK(frame_fault(d, even, rb, 16, 4, rb * t.rows) != nullptr, "%d: a frame of `limit` bytes", t.pix);
+        CHECK(frame_fault(d, even, rb - 2, 16, 4, 1u << 30) != nullptr, "%d: a pitch below the row", t.pix);
+        CHECK(frame_fault(d, nullptr, rb, 16, 4, 1u << 30) != nullptr, "%d: a NULL frame", t.pix);
+        CHECK((frame_fault(d, even + 1, rb, 16, 4, 1u << 30) != nullptr) == (d.bytes == 2), "%d: an odd base", t.pix);
+        CHECK((frame_fault(d, even, rb + 1, 16, 4, 1u << 30) != nullptr) == (d.bytes == 2), "%d: an odd pitch", t.pix);
+    }
+    CHECK(layout_of(2).bytes == 0 && layout_of(-1).bytes == 0 && layout_of(36).bytes == 0, "values that are no layout");
+}
+
+void check_row_chunks() {
+    CHECK(kChunk == 16, "a chunk is one 16-byte store");
+    for (int n : {0, 1, 15, 16, 17, 31, 33})
+        for (uintptr_t align = 0; align < 16; align++) {
+            const uintptr_t a = 0x4000u + align;
+            const int items = (int)row_items(n);
+            int next = 0;  // the first byte no item has covered yet
+            for (int k = 0; k < items + 2; k++) {
+                struct {
+                    int b0, len;
+                } c{0, 0};  // the item as the callers read it: the head, a chunk, or nothing past the row's end
+                const RowChunk rc = row_chunk(a, n, k);
+                if (k == 0)
+                    c = {0, rc.head};
+                else if (rc.b0 < n)
+                    c = {rc.b0, rc.len(n)};
+                CHECK(c.len >= 0 && c.len <= kChunk, "n=%d align=%d item %d: len %d", n, (int)align, k, c.len);
+                if (c.len == 0) continue;
+                CHECK(k < items, "n=%d align=%d: item %d past row_items writes", n, (int)align, k);
+                CHECK(c.b0 == next, "n=%d align=%d item %d: starts at %d, want %d", n, (int)align, k, c.b0, next);
+                CHECK(c.len != kChunk || ((a + (uintptr_t)c.b0) & 15u) == 0, "n=%d align=%d item %d: a full chunk off its boundary", n,
+                      (int)align, k);
+                CHECK(k == 0 || ((a + (uintptr_t)c.b0) & 15u) == 0, "n=%d align=%d item %d: a chunk off its boundary", n, (int)align, k);
+                next = c.b0 + c.len;
+            }
+            CHECK(next == n, "n=%d align=%d: the items cover %d bytes", n, (int)align, next);
+        }
+}
+
 template <class L>
 void check_descriptor(int pix) {
     const LayoutDesc d = layout_of(pix), t = L::desc;
@@ -469,6 +548,8 @@ void check_layout(int pix) {
 int main() {
     check_bytes();
     check_samples();
+    check_planes();
+    check_row_chunks();
     for (int pix : {0, 1, 2, 15, 20, 31, 36, -1}) CHECK(!converted_format(pix) && !layout_of(pix).converted(), "%d is no converted format", pix);
     check_layout<LayoutUyvy>(UYVY);
     check_layout<LayoutYuyv>(YUYV);

@@ -272,6 +272,31 @@ def test_gpu_async_planar_registers_column_halves(ox):
     am.close()
 
 
+@pytest.mark.parametrize("out_fmt", ["yuv420p", "nv12"])
+def test_gpu_async_registered_odd_chroma_column(ox, out_fmt):
+    """Output 268 x 128 in two halves: r.x = r.w = 134 and an odd chroma column c.x = c.w = 67, the mappers scaling
+    rigA's 512 x 256 to 134 x 128.  The same frame through registered planes (pitch = width + 6: the region
+    downloads write them) and through unregistered ones (staging and copy-out): byte-identical, and nothing but
+    the regions' bytes is written.  (push_device with such regions: test_gpu_async_device_ragged_regions.)"""
+    t = golden("rigA")
+    OW, OH = 268, 128
+    am = ox.AsyncMultiMapper([template(ox, t) for _ in range(2)], t["sizes"], (OW, OH), [0, 0], [0, 0],
+                             [(0.0, 0.0, 0.5, 1.0), (0.5, 0.0, 0.5, 1.0)])
+    am.set_pixel_formats("yuv420p", out_fmt)
+    reg, plain = new_out(OW, OH, out_fmt, pad=6), new_out(OW, OH, out_fmt, pad=6)
+    am.register_output(reg)
+    fr = smooth_frames(t, 5500)
+    for out in (reg, plain):
+        push(am, t, fr, out, "yuv420p")
+    assert am.pop() is reg and am.pop() is plain
+    for k, (a, b) in enumerate(zip(reg, plain)):
+        assert np.array_equal(a, b), (out_fmt, "plane %d" % k, np.argwhere(a != b)[:6].tolist())
+        assert (padding_of(a) == FILL).all() and (padding_of(b) == FILL).all(), (out_fmt, k)
+    assert (plain[0] != FILL).any() and (plain[1][:, 2 * 67 if out_fmt == "nv12" else 67:] != FILL).any()
+    am.unregister_output(reg)
+    am.close()
+
+
 # ---- 5. preview ----------------------------------------------------------------------------------------
 def test_gpu_async_nv12_preview(ox):
     """NV12 in and out with a preview and two regions: the preview stays RGB and equals the planar pipeline's
