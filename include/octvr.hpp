@@ -454,6 +454,26 @@ private:
     }
 };
 
+// The tensor of Mapper::stitch_tensor: octvr_tensor_out with scale 1 and bias 0, and contiguous planes from a
+// size (strides in elements: row_stride = w, plane_stride = w * h).  dtype: OCTVR_TENSOR_U8 / _F16 / _F32.
+struct TensorOut : octvr_tensor_out {
+    TensorOut() : octvr_tensor_out() {
+        for (int c = 0; c < 3; c++) {
+            scale[c] = 1.f;
+            bias[c] = 0.f;
+        }
+    }
+    TensorOut(void* device_ptr, cv::Size size, int type, bool bgr_order = false) : TensorOut() {
+        dev = device_ptr;
+        w = size.width;
+        h = size.height;
+        dtype = type;
+        bgr = bgr_order ? 1 : 0;
+        row_stride = (size_t)(size.width > 0 ? size.width : 0);
+        plane_stride = row_stride * (size_t)(size.height > 0 ? size.height : 0);
+    }
+};
+
 // vr::Mapper (modules/octvr/src/mapper.hpp:29-95): one rig's per-frame stitch on the GPU.
 class Mapper {
 public:
@@ -544,6 +564,27 @@ public:
                                                       (int)gains.size(), nullptr));
         }
         detail::check(octvr_stream_sync(nullptr));
+    }
+    // The RGB result as a planar u8 / f16 / f32 tensor for a model (no reference counterpart; octvr_hip.h
+    // octvr_mapper_stitch_tensor).  inputs / pitches: the device frames in the mapper's input format, one per
+    // input and overlay; out_or_null: the YUV frame in the mapper's output format, or nullptr for none.  A tensor
+    // of the size prepare_preview() prepared is gathered from the source frames (any number of frames in flight,
+    // no composite launch without a YUV frame); any other size is resized from the result frame.  With stream ==
+    // nullptr it returns after the stitch has completed, as stitch() does; else it is ordered on that HIP stream.
+    void stitch_tensor(const std::vector<const uint8_t*>& inputs, const std::vector<size_t>& pitches, uint8_t* out_or_null,
+                       size_t out_pitch, const TensorOut& tensor, const std::vector<double>& gains = std::vector<double>(),
+                       void* stream = nullptr) {
+        if ((int)inputs.size() != n_ || pitches.size() != inputs.size())
+            throw cv::Exception(OCTVR_E_INVALID, "input count does not match the mapper");
+        detail::check(octvr_mapper_stitch_tensor(m_.get(), inputs.data(), pitches.data(), out_or_null, out_pitch, &tensor,
+                                                 gains.empty() ? nullptr : gains.data(), (int)gains.size(), stream));
+        if (!stream) detail::check(octvr_stream_sync(nullptr));
+    }
+    // A w x h tensor (or preview) without the result frame from now on (octvr_mapper_prepare_preview): blend 0 and
+    // the output at template size only; 0 x 0 drops it.
+    void prepare_preview(cv::Size size) {
+        detail::check(octvr_mapper_prepare_preview(m_.get(), rig_.get(), size.width, size.height));
+        prepared_ = size;
     }
     std::vector<double> gains() const {
         std::vector<double> g(n_gains_);  // one per input; overlays have none

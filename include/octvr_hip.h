@@ -216,6 +216,43 @@ int octvr_mapper_stitch_preview(octvr_mapper* mapper, const uint8_t* const* in_d
  * does not change.  preview_w * preview_h <= OCTVR_MAX_PREPARED_PREVIEW_PIXELS (OCTVR_E_INVALID above). */
 #define OCTVR_MAX_PREPARED_PREVIEW_PIXELS (1 << 26)
 int octvr_mapper_prepare_preview(octvr_mapper* mapper, const octvr_rig* rig, int preview_w, int preview_h);
+/* The RGB result as a planar tensor (no reference counterpart): what a model takes, with no packed-RGB or 4:2:0
+ * detour.  Let P[y][x][c] be the bytes octvr_mapper_stitch_preview writes for a w x h preview of the same
+ * stitch (at template size: the RGB result itself).  Element (plane, y, x) is stored at
+ * dev + plane * plane_stride + y * row_stride + x elements and holds colour c of pixel (x, y), c = plane for
+ * bgr = 0 and 2 - plane for bgr = 1:
+ *   OCTVR_TENSOR_U8   P
+ *   OCTVR_TENSOR_F32  (float)P * scale[c] + bias[c], a multiply and then an add in f32 (two roundings)
+ *   OCTVR_TENSOR_F16  that f32 value rounded to nearest even; overflow gives inf, subnormal halves are kept
+ * scale and bias are indexed by colour R, G, B whatever `bgr` says, and ignored for U8.  A float tensor at a
+ * resized size goes through the preview's u8 rounding.  Elements between w and row_stride, and between planes,
+ * are never written.  dev needs the element size's alignment only; rows at wider alignments get wider stores.
+ * out_dev non-NULL: the YUV frame of octvr_mapper_stitch_yuv420p as well, the same bytes and gains, in the
+ * mapper's output format.  out_dev NULL: no YUV frame is written and out_pitch is ignored.
+ * The tensor takes one of the preview's two paths.  Of the size octvr_mapper_prepare_preview prepared it is
+ * gathered from the source frames: any number of frames in flight, and with out_dev NULL no composite is launched
+ * at all (the gain feed or set_gains, then the gather).  Of any other size it is resized from the result frame,
+ * which serves every mapper (blends, scaled output, overlays, texture mode, any input format), needs one frame in
+ * flight as the preview does (OCTVR_E_INVALID otherwise), and with out_dev NULL skips the conversion to YUV.
+ * OCTVR_E_INVALID before any launch, the mapper left usable: tensor or dev NULL, a dtype outside the enum, bgr
+ * outside {0, 1}, w or h <= 0, row_stride < w, plane_stride < row_stride * (h - 1) + w, dev not a multiple of the
+ * element size.  The kernels address with 64 bits: a tensor may reach 2 GiB and more from dev.
+ * octvr_mapper_info counts "tensor_resized", "tensor_gathered" and "tensor_no_composite" (gathered tensors whose
+ * stitch launched no composite); the timed interval (octvr_mapper_set_timing) covers the stitch and the tensor
+ * kernel. */
+enum { OCTVR_TENSOR_U8 = 0, OCTVR_TENSOR_F16 = 1, OCTVR_TENSOR_F32 = 2 };
+typedef struct octvr_tensor_out {
+    void* dev;            /* device memory of the mapper's device */
+    int w, h;             /* picture size: any size a preview may have */
+    int dtype;            /* OCTVR_TENSOR_* */
+    int bgr;              /* 0: planes R, G, B;  1: planes B, G, R */
+    size_t row_stride;    /* in elements, >= w */
+    size_t plane_stride;  /* in elements, >= row_stride * (h - 1) + w (planes do not overlap) */
+    float scale[3], bias[3]; /* per colour R, G, B whatever `bgr` says; ignored for U8 */
+} octvr_tensor_out;
+int octvr_mapper_stitch_tensor(octvr_mapper* mapper, const uint8_t* const* in_dev, const size_t* in_pitch,
+                               uint8_t* out_dev /* may be NULL */, size_t out_pitch, const octvr_tensor_out* tensor,
+                               const double* gains, int n_gains, void* stream);
 /* Mapper::gains() (mapper.hpp:88-90): gains used by the last stitch, one per input (n >= N; overlays have
  * none) (synchronizes the stream). */
 int octvr_mapper_gains(octvr_mapper* mapper, double* gains, int n);

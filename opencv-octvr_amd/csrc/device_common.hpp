@@ -169,6 +169,13 @@ typedef __attribute__((address_space(4))) const SourceFrame kSourceFrame;
 // wave-uniform value -> SGPR (scalar loads / branches downstream)
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// Lane `sel` of each quad's value in every lane of the quad: one v_mov_b32 with a quad-permute DPP control
+// (quad_perm:[sel, sel, sel, sel]); every lane of the wave is active where this is called.
+template <int SEL>
+__device__ __forceinline__ uint32_t quad_lane(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, SEL * 0x55, 0xF, 0xF, false);
+}
+
 struct Taps {
     uint32_t c[4];  // packed RGBA of the 4 taps (0 when outside / invalid)
     uint32_t fx, fy;

@@ -615,6 +615,26 @@ struct PreviewList {
 hipError_t launch_preview_gather(const FrameSet& frames, const PreviewList& list, const double* gains, int use_gain,
                                  uint8_t* out, int64_t out_pitch, hipStream_t s, int pix = 0);
 
+// ---- the RGB result as a planar tensor (tensor_out.hip) -----------------------------------------
+// octvr_mapper_stitch_tensor: the bytes P of a w x h preview (above) as three planes of u8, f16 or f32.
+// Element (plane, y, x) is at dev + plane * plane_stride + y * row_stride + x elements and holds colour
+// c = bgr ? 2 - plane : plane of pixel (x, y): P for u8, (float)P * scale[c] + bias[c] (a multiply, then an
+// add) for f32, that value rounded to nearest even for f16.  Offsets are 64-bit; the host checks the strides.
+constexpr int kTensorU8 = 0, kTensorF16 = 1, kTensorF32 = 2;  // OCTVR_TENSOR_*
+struct TensorPlanes {
+    void* dev;
+    int64_t row_stride, plane_stride;  // elements
+    int32_t w, h;
+    int32_t dtype, bgr;
+    float scale[3], bias[3];  // per colour R, G, B
+};
+// From the RGBA result frame (sw x sh, 4 bytes per pixel at spitch): resize_rgba_rgb_kernel's arithmetic.
+hipError_t launch_tensor_resize(const uint8_t* rgba, int sw, int sh, int64_t spitch, const TensorPlanes& t, hipStream_t s);
+// From the source frames through the prepared tap list (t.w x t.h = list.dw x list.dh): preview_gather_kernel's
+// arithmetic.  gains: a frame slot's kMaxCams doubles.  pix: kPixInNv12.
+hipError_t launch_tensor_gather(const FrameSet& frames, const PreviewList& list, const double* gains, int use_gain,
+                                const TensorPlanes& t, hipStream_t s, int pix = 0);
+
 hipError_t launch_selftest_sat(const float* in, uint8_t* out, int n, int method, hipStream_t s);
 
 }  // namespace octvr

@@ -93,6 +93,39 @@ void check_out_frame(const octvr_mapper* m, const uint8_t* out_dev, size_t out_p
     REQUIRE(!why, std::string("output ") + why);
 }
 
+// The caller's tensor (octvr_hip.h octvr_tensor_out), checked before anything is put on the stream, as the
+// kernels' view of it.  The kernels form 64-bit element offsets, so a tensor may reach any distance from dev;
+// the strides are bounded so that no offset of a row overflows.
+TensorPlanes check_tensor(const octvr_tensor_out* t) {
+    REQUIRE(t && t->dev, "NULL tensor");
+    REQUIRE(t->dtype == OCTVR_TENSOR_U8 || t->dtype == OCTVR_TENSOR_F16 || t->dtype == OCTVR_TENSOR_F32,
+            "tensor dtype must be OCTVR_TENSOR_U8, OCTVR_TENSOR_F16 or OCTVR_TENSOR_F32");
+    REQUIRE(t->bgr == 0 || t->bgr == 1, "tensor bgr must be 0 or 1");
+    REQUIRE(t->w > 0 && t->h > 0, "bad tensor size");
+    REQUIRE(t->row_stride >= (size_t)t->w && t->row_stride < ((size_t)1 << 31),
+            "tensor row stride below its width (or 2^31 elements and more)");
+    REQUIRE(t->plane_stride >= t->row_stride * (size_t)(t->h - 1) + (size_t)t->w && t->plane_stride < ((size_t)1 << 58),
+            "tensor planes overlap (or a plane stride of 2^58 elements and more)");
+    const size_t es = t->dtype == OCTVR_TENSOR_U8 ? 1 : t->dtype == OCTVR_TENSOR_F16 ? 2 : 4;
+    REQUIRE(reinterpret_cast<uintptr_t>(t->dev) % es == 0, "tensor not aligned to its element size");
+    // one workgroup per row segment of at least 64 pixels (tensor_out.hip)
+    REQUIRE(((uint64_t)t->w + 63) / 64 * (uint64_t)t->h < 0x7FFFFFFFull, "tensor too large");
+    TensorPlanes p;
+    memset(&p, 0, sizeof p);
+    p.dev = t->dev;
+    p.row_stride = (int64_t)t->row_stride;
+    p.plane_stride = (int64_t)t->plane_stride;
+    p.w = t->w;
+    p.h = t->h;
+    p.dtype = t->dtype;
+    p.bgr = t->bgr;
+    for (int c = 0; c < 3; c++) {
+        p.scale[c] = t->scale[c];
+        p.bias[c] = t->bias[c];
+    }
+    return p;
+}
+
 // The kernels' view of one frame's inputs.
 FrameSet frame_set(const octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch) {
     FrameSet fs;
@@ -336,8 +369,8 @@ void mapper_set_conv(octvr_mapper* m, int in_fmt, int out_fmt) {
 // same inputs, copied stream-ordered (AsyncMultiMapper's gain_modes chaining, async.cpp:78-86).
 void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch, uint8_t* out_dev,
                    size_t out_pitch, const double* gains, int n_gains, const double* gains_dev, hipStream_t s,
-                   const PreviewOut* preview) {
-    REQUIRE(m && in_dev && in_pitch && out_dev, "NULL argument");
+                   const PreviewOut* preview, const octvr_tensor_out* tensor) {
+    REQUIRE(m && in_dev && in_pitch && (out_dev || tensor) && !(preview && tensor), "NULL argument");
     // a preview of the prepared size is gathered from the source frames after the composite (preview.hip):
     // the stitch itself is the one without a preview
     const bool gathered = preview && m->pv.view.dw > 0 && preview->w == m->pv.view.dw && preview->h == m->pv.view.dh;
@@ -350,7 +383,18 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
             ensure_result(*m);
         }
     }
-    check_out_frame(m, out_dev, out_pitch);
+    // a tensor is chosen as a preview is: of the prepared size it is gathered from the source frames
+    // (tensor_out.hip), of any other it is resized from the result frame
+    TensorPlanes tp;
+    const bool tensor_gathered = tensor && m->pv.view.dw > 0 && tensor->w == m->pv.view.dw && tensor->h == m->pv.view.dh;
+    if (tensor) {
+        tp = check_tensor(tensor);
+        if (!tensor_gathered) {
+            REQUIRE(m->slots.size() == 1, "tensor output needs one frame in flight");
+            ensure_result(*m);
+        }
+    }
+    if (out_dev) check_out_frame(m, out_dev, out_pitch);
     DeviceGuard dg(m->device);
     // converted sides: the slot's unpack launch fills its NV12 input frames, which every stage below reads,
     // and the stitch writes the slot's NV12 output frame, which the pack launch converts at the end
@@ -366,7 +410,7 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
     hipEvent_t e0 = ev.e0, e1 = ev.e1;
     const bool timed = e0 != nullptr;
     // the events bracket the conversions too
-    const bool outer = m->scaled || m->mb || preview || m->conv_in || m->conv_out;
+    const bool outer = m->scaled || m->mb || preview || tensor || m->conv_in || m->conv_out;
     if (m->conv_in) {
         if (timed) HIP_CHECK(hipEventRecord(e0, s));
         fs = conv_unpack_slot(m, sl, us, s);
@@ -374,14 +418,15 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
     stitch_gains(m, sl, fs, gains, gains_dev, s);
     uint8_t* const caller_out = out_dev;
     const size_t caller_pitch = out_pitch;
-    if (m->conv_out) {
+    const bool pack = m->conv_out && out_dev;
+    if (pack) {
         out_dev = sl.conv_out;
         out_pitch = (size_t)m->SW;
     }
     // overlays after a blend are copied onto the RGB(A) result too (mapper.cpp:279-287)
     const bool overlays = m->ov.view.n_groups > 0;
     if (timed && outer && !m->conv_in) HIP_CHECK(hipEventRecord(e0, s));  // else the composite records its own
-    if (m->scaled || (preview && !gathered) || overlays) {
+    if (m->scaled || (preview && !gathered) || (tensor && !tensor_gathered) || overlays) {
         // stitch at template size into the RGB(A) result, then resize + RGB -> YUV420P (mapper.cpp:290-306)
         // (one frame slot only: the result frame is shared); without scaling the resize is the identity
         if (m->mb)
@@ -390,8 +435,13 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
             HIP_CHECK(launch_mb_remap(fs, m->tiles.view, sl.gains, m->use_gain,
                                       RgbaOut{m->result.p, (uint32_t)m->result.n, m->result_view.p}, s, m->pix));
         if (overlays) HIP_CHECK(launch_overlay_apply(fs, m->ov.view, m->result.p, (int64_t)m->W * 4, s, m->pix));
-        HIP_CHECK(launch_resize_rgba_yuv420(m->result.p, m->W, m->H, (int64_t)m->W * 4, out_dev, m->SW, m->SH,
-                                            (int64_t)out_pitch, s, (m->pix & kPixOutNv12) != 0));
+        if (out_dev)
+            HIP_CHECK(launch_resize_rgba_yuv420(m->result.p, m->W, m->H, (int64_t)m->W * 4, out_dev, m->SW, m->SH,
+                                                (int64_t)out_pitch, s, (m->pix & kPixOutNv12) != 0));
+        if (tensor) {  // never the gathered one: a prepared size needs blend 0, no scaling and no overlay pass
+            HIP_CHECK(launch_tensor_resize(m->result.p, m->W, m->H, (int64_t)m->W * 4, tp, s));
+            m->tensor_resized++;
+        }
         if (preview)  // cuda::resize(result, preview_output, ...) (mapper.cpp:308-312)
             HIP_CHECK(launch_resize_rgba_rgb(m->result.p, m->W, m->H, (int64_t)m->W * 4, preview->dev, preview->w,
                                              preview->h, (int64_t)preview->pitch, s));
@@ -401,13 +451,19 @@ void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* 
         TiledLut view = m->tiles.view;
         view.queue = sl.queue;
         // with a gathered preview the events above and below bracket the composite and the preview kernel
-        HIP_CHECK(launch_stitch(fs, view, m->W, m->H, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s,
-                                outer ? nullptr : e0, outer ? nullptr : e1, m->pix));
+        if (out_dev)  // a gathered tensor alone reads the source frames itself: no composite
+            HIP_CHECK(launch_stitch(fs, view, m->W, m->H, sl.gains, m->use_gain, out_dev, (int64_t)out_pitch, s,
+                                    outer ? nullptr : e0, outer ? nullptr : e1, m->pix));
+        if (tensor_gathered) {
+            HIP_CHECK(launch_tensor_gather(fs, m->pv.view, sl.gains, m->use_gain, tp, s, m->pix));
+            m->tensor_gathered++;
+            if (!out_dev) m->tensor_no_composite++;
+        }
         if (gathered)
             HIP_CHECK(launch_preview_gather(fs, m->pv.view, sl.gains, m->use_gain, preview->dev, (int64_t)preview->pitch, s,
                                             m->pix));
     }
-    if (m->conv_out) conv_pack(m, sl.conv_out, caller_out, caller_pitch, s);
+    if (pack) conv_pack(m, sl.conv_out, caller_out, caller_pitch, s);
     if (timed && outer) HIP_CHECK(hipEventRecord(e1, s));
     ev.keep();
     finish_slot(sl, s);

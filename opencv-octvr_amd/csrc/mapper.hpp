@@ -52,6 +52,9 @@ struct octvr_mapper {
     // frames after the composite, on the frame slot's gains, and needs no result frame.
     octvr::PreviewListDev pv;
     std::vector<int> rois;  // x, y, w, h per camera: what prepare_preview checks its rig against
+    // octvr_mapper_stitch_tensor so far: tensors resized from the result frame, tensors gathered through the
+    // prepared list, and the gathered ones whose stitch launched no composite (no YUV frame asked for)
+    uint64_t tensor_resized = 0, tensor_gathered = 0, tensor_no_composite = 0;
     // Per-frame device state that consecutive stitches would otherwise share: the gains, the feed's
     // pair totals and tickets, the composite's work queue.  A mapper is created with one slot;
     // octvr_mapper_set_frames_in_flight adds slots so that stitches issued on different streams overlap
@@ -118,9 +121,11 @@ struct PreviewOut {
     int w, h;
     size_t pitch;
 };
+// tensor (octvr_mapper_stitch_tensor; not together with a preview): the RGB result as planes.  Only then may
+// out_dev be NULL: no YUV frame is written, and a tensor of the prepared preview size launches no composite.
 void mapper_stitch(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch, uint8_t* out_dev,
                    size_t out_pitch, const double* gains, int n_gains, const double* gains_dev, hipStream_t s,
-                   const PreviewOut* preview = nullptr);
+                   const PreviewOut* preview = nullptr, const octvr_tensor_out* tensor = nullptr);
 void mapper_stitch_batch(octvr_mapper* m, int nb, const uint8_t* const* in_dev, const size_t* in_pitch,
                          uint8_t* const* out_dev, size_t out_pitch, const double* gains, hipStream_t s);
 // octvr_mapper_prepare_preview: the tap list of a w x h preview from `rig` (the rig the mapper was created

@@ -356,6 +356,15 @@ int octvr_mapper_stitch_preview(octvr_mapper* m, const uint8_t* const* in_dev, c
     });
 }
 
+int octvr_mapper_stitch_tensor(octvr_mapper* m, const uint8_t* const* in_dev, const size_t* in_pitch, uint8_t* out_dev,
+                               size_t out_pitch, const octvr_tensor_out* tensor, const double* gains, int n_gains,
+                               void* stream) {
+    return guarded([&] {
+        REQUIRE(tensor && tensor->dev, "NULL tensor");
+        mapper_stitch(m, in_dev, in_pitch, out_dev, out_pitch, gains, n_gains, nullptr, (hipStream_t)stream, nullptr, tensor);
+    });
+}
+
 int octvr_mapper_prepare_preview(octvr_mapper* m, const octvr_rig* rig, int preview_w, int preview_h) {
     return guarded([&] { mapper_prepare_preview(m, rig, preview_w, preview_h); });
 }
@@ -509,6 +518,8 @@ int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
         std::string js = tmp;
         js += ", \"preview_prepared\": [" + std::to_string(m->pv.view.dw) + ", " + std::to_string(m->pv.view.dh) +
               "], \"preview_entries\": " + std::to_string(m->pv.view.n_entries);
+        js += ", \"tensor_resized\": " + std::to_string(m->tensor_resized) + ", \"tensor_gathered\": " +
+              std::to_string(m->tensor_gathered) + ", \"tensor_no_composite\": " + std::to_string(m->tensor_no_composite);
         // converted sides, per family of layouts (0: the side is not of the family): the footprint runs the unpack
         // launch converts and the packed bytes it reads per frame (run_bpp(): 4, 6 or 8 per pixel of a piece's row),
         // the bytes of the frame the pack launch writes

@@ -5,13 +5,6 @@
 
 namespace octvr {
 
-// Lane `sel` of each quad's value in every lane of the quad: one v_mov_b32 with a quad-permute DPP control
-// (quad_perm:[sel, sel, sel, sel]); every lane of the wave is active where this is called.
-template <int SEL>
-__device__ __forceinline__ uint32_t quad_lane(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, SEL * 0x55, 0xF, 0xF, false);
-}
-
 // One lane per result tap, one quad per preview pixel, 64 preview pixels per workgroup: entry t = 4 pixel +
 // tap is one coalesced 8-byte load per lane.  The lane computes what the MODE-1 composite stores into the
 // result frame for its tap's result pixel — the four source taps gathered in place (gather_taps: YUV -> RGB,

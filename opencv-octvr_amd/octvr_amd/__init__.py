@@ -79,6 +79,19 @@ _lib.octvr_mapper_stitch_preview.argtypes = [_VP, C.POINTER(_VP), C.POINTER(C.c_
                                              C.c_int, C.c_size_t, C.POINTER(C.c_double), C.c_int, _VP]
 if hasattr(_lib, "octvr_mapper_prepare_preview"):  # (absent from older libraries OCTVR_HIP_LIB may select for an A/B)
     _lib.octvr_mapper_prepare_preview.argtypes = [_VP, _VP, C.c_int, C.c_int]
+TENSOR_U8, TENSOR_F16, TENSOR_F32 = 0, 1, 2  # OCTVR_TENSOR_*
+
+
+class TensorOut(C.Structure):
+    """octvr_tensor_out: three planes of u8 / f16 / f32 on the device, strides in elements."""
+    _fields_ = [("dev", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("dtype", C.c_int), ("bgr", C.c_int),
+                ("row_stride", C.c_size_t), ("plane_stride", C.c_size_t), ("scale", C.c_float * 3),
+                ("bias", C.c_float * 3)]
+
+
+if hasattr(_lib, "octvr_mapper_stitch_tensor"):
+    _lib.octvr_mapper_stitch_tensor.argtypes = [_VP, C.POINTER(_VP), C.POINTER(C.c_size_t), _VP, C.c_size_t,
+                                                C.POINTER(TensorOut), C.POINTER(C.c_double), C.c_int, _VP]
 _lib.octvr_mapper_gains.argtypes = [_VP, C.POINTER(C.c_double), C.c_int]
 _lib.octvr_mapper_set_frames_in_flight.argtypes = [_VP, C.c_int]
 if hasattr(_lib, "octvr_mapper_set_pixel_formats"):  # (absent from libraries built before NV12: scripts/ab.sh variants)
@@ -791,6 +804,58 @@ class Mapper:
         path.  Blend 0 and unscaled output only (OctvrError E_UNSUPPORTED otherwise); a second call replaces
         the size, (0, 0) drops it.  Synchronizes."""
         _check(_lib.octvr_mapper_prepare_preview(self._h, self._mt._h, int(w), int(h)))
+
+    def stitch_tensor(self, inputs, tensor, output=None, gains=None, stream=None, order="rgb", scale=None, bias=None):
+        """The RGB result as a planar tensor for a model (octvr_mapper_stitch_tensor).  tensor: a (3, h, w) cuda
+        tensor of uint8, float16 or float32 with stride(2) == 1; stride(0) and stride(1) are the plane and row
+        strides, so a view into a batch tensor works.  Plane p holds colour p of order ("rgb" or "bgr") of the
+        bytes P a (h, w, 3) preview of the same stitch would hold: P for uint8, P * scale[c] + bias[c] in float32
+        (a multiply, then an add; rounded to nearest even for float16) otherwise.  scale, bias: a scalar or three
+        values for R, G, B (defaults 1 and 0; ignored for uint8).  output: the YUV frame as stitch() writes it, or
+        None for no YUV frame.  A tensor of the size prepare_preview prepared is gathered from the source frames
+        (any number of frames in flight; with output=None no composite is launched); any other size is resized
+        from the result frame and needs one frame in flight."""
+        dtypes = {torch.uint8: TENSOR_U8, torch.float16: TENSOR_F16, torch.float32: TENSOR_F32}
+        if not isinstance(tensor, torch.Tensor) or tensor.dim() != 3 or tensor.shape[0] != 3:
+            raise ValueError("tensor must be a torch tensor of shape (3, h, w)")
+        if tensor.dtype not in dtypes:
+            raise ValueError("tensor dtype must be uint8, float16 or float32")
+        if tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise ValueError("tensor must be on the mapper's device cuda:%d" % self.device)
+        if tensor.shape[1] < 1 or tensor.shape[2] < 1 or (tensor.shape[2] > 1 and tensor.stride(2) != 1):
+            raise ValueError("tensor needs stride(2) == 1 (planes of contiguous rows)")
+        if order not in ("rgb", "bgr"):
+            raise ValueError("order must be 'rgb' or 'bgr'")
+
+        def three(v, default, name):
+            if v is None:
+                v = default
+            vals = [float(x) for x in np.asarray(v, dtype=np.float32).reshape(-1)]
+            if len(vals) == 1:
+                vals = vals * 3
+            if len(vals) != 3:
+                raise ValueError("%s takes a scalar or three values (R, G, B)" % name)
+            return (C.c_float * 3)(*vals)
+
+        t = TensorOut(tensor.data_ptr(), tensor.shape[2], tensor.shape[1], dtypes[tensor.dtype], int(order == "bgr"),
+                      max(tensor.stride(1), 0), max(tensor.stride(0), 0), three(scale, 1.0, "scale"),
+                      three(bias, 0.0, "bias"))
+        if isinstance(inputs, FrameRefs):
+            n, ptrs, pitches = inputs.n, inputs.ptrs, inputs.pitches
+        else:
+            n = len(inputs)
+            ptrs = (_VP * n)(*[x.data_ptr() for x in inputs])
+            pitches = (C.c_size_t * n)(*[x.stride(0) for x in inputs])
+        if n != self.n:
+            raise ValueError("stitch takes %d frames (every input, then every overlay), got %d" % (self.n, n))
+        g = None
+        ng = 0
+        if gains is not None:
+            g = (C.c_double * len(gains))(*gains)
+            ng = len(gains)
+        out_ptr = C.c_void_p(output.data_ptr()) if output is not None else None
+        _check(_lib.octvr_mapper_stitch_tensor(self._h, ptrs, pitches, out_ptr, output.stride(0) if output is not None else 0,
+                                               C.byref(t), g, ng, _stream_ptr(stream)))
 
     @staticmethod
     def batch_refs(frame_sets, outputs):
