@@ -515,7 +515,7 @@ struct MbBlendArgs {
     const uint2* work;              // multi-band (or NULL): the sub-tiles to blend, 4 per workgroup (wave w of
                                     // block b takes work[4 b + w]): x = tile | quarter << 24 | owned << 27,
                                     // y = the sub-tile's cameras; padded with owned = 3 (nothing to do)
-    int n_work;                     // their count (a multiple of 4, when work is set)
+    int n_work;                     // their count, a multiple of 4 (0: nothing to launch); -1 without a list
     const MbCamLevel* cams;         // this level
     const MbCamLevel* cams_next;    // level + 1 (NULL at the top)
     const uint8_t* g;               // this level's pyramid allocation

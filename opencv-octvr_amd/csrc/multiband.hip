@@ -525,8 +525,11 @@ __global__ void __launch_bounds__(256, kBlendWaves) mb_blend_kernel(MbBlendArgs 
 
 hipError_t launch_mb_blend(const MbBlendArgs& a, hipStream_t s) {
     const int tiles_y = (a.H + kTileH - 1) / kTileH;
-    const int n = a.work ? a.n_work / 4 : a.tiles_x * tiles_y;  // (the list: 4 sub-tiles per workgroup)
-    if (n <= 0) return hipSuccess;
+    // n_work >= 0: the list, 4 sub-tiles per workgroup; -1: every tile.  By the count, not the pointer: an empty
+    // list (every sub-tile deep and written by the remap, or unread) has no device array, and must launch nothing
+    // rather than blend every tile from Gaussian levels nobody wrote, over the remap's results
+    const int n = a.n_work >= 0 ? a.n_work / 4 : a.tiles_x * tiles_y;
+    if (n <= 0 || (a.n_work > 0 && !a.work)) return n <= 0 ? hipSuccess : hipErrorInvalidValue;
     hipLaunchKernelGGL(mb_blend_kernel, dim3(n), dim3(256), 0, s, a);
     return hipGetLastError();
 }

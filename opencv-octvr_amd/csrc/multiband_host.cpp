@@ -420,7 +420,10 @@ std::string multiband_info(const MultiBand& M) {
                               ", \"unread_subtiles\": " + std::to_string(L.n_skip)).c_str() : "");
         s += buf;
     }
-    return s + "]";
+    s += "]";
+    // the level-0 remap's tiled LUT: the build statistics the blend = 0 composite reports at the top level
+    if (!M.remap.stats.empty()) s += ", \"remap_lut\": {" + M.remap.stats + "}";
+    return s;
 }
 
 }  // namespace octvr

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "host_common.hpp"
@@ -319,6 +320,7 @@ TiledLutBuild build_tiled_lut(const std::vector<TileJob>& jobs, const EntryFn& e
     }
     b.n_items = n_items;
     b.n_wide = (int)b.wide_tiles.size();
+    size_t black_groups = 0, black_groups1 = 0;  // statistics: staged groups outside the image, in all and in grp1
     {  // unique source bytes the launch reads: the union over items of the staged groups (8 luma bytes per
        // group row, 4 U + 4 V bytes per group row pair), plus the wide tiles' tap cells
         const int nc = (int)in_w.size();
@@ -342,8 +344,15 @@ TiledLutBuild build_tiled_lut(const std::vector<TileJob>& jobs, const EntryFn& e
                 const TileSlot& sl = b.slots[(size_t)t * kTileSlots + j];
                 const uint16_t* g = c < kGroupFirst ? b.grp0.data() + ((size_t)t * kGroupFirst + c) * 64
                                                      : b.grp1.data() + ((size_t)(b.hdr[t].stride >> kStrideBits) + c - kGroupFirst) * 64;
-                for (int i = 0; i < 64; i++)
-                    if (g[i] & kGroupValid) mark(sl.cam, sl.bx0 + 8 * ((g[i] >> 8) & 31), sl.by0 + (g[i] & 255));
+                for (int i = 0; i < 64; i++) {
+                    if (!(g[i] & kGroupValid)) continue;
+                    const int gx = sl.bx0 + 8 * ((g[i] >> 8) & 31), gy = sl.by0 + (g[i] & 255);
+                    mark(sl.cam, gx, gy);
+                    // a staged group past the image's right or bottom edge (staged as black, composite.hip kStageBlack)
+                    const bool black = gx >= in_w[sl.cam] || gy >= in_h[sl.cam];
+                    black_groups += black;
+                    black_groups1 += black && c >= kGroupFirst;
+                }
             }
         }
         for (const CompositeEntry& e : b.wide) {
@@ -376,14 +385,31 @@ TiledLutBuild build_tiled_lut(const std::vector<TileJob>& jobs, const EntryFn& e
         const int n_bins = (int)(sizeof(edges) / sizeof(edges[0])) - 1;
         std::vector<long> hist(n_bins, 0), lds_hist(7, 0);
         std::vector<long> band_chunks(kStitchBands, 0);
+        // the staging paths an item takes in the composite: its slot count, whether it has overflow chunks (grp1) and
+        // whether a slot past the first starts among them (found by stage_slot's search) or before them (the map word)
+        long by_slots[kTileSlots + 1] = {}, late_slot = 0, early_slot = 0, overflow = 0;
+        uint32_t max_chunks = 0, max_lds = 0, max_stride = 0;
         for (int t = 0; t < n_items; t++) {
-            const int ch = (int)((b.hdr[t].nslots >> 8) & 0xFFu);
+            const int ns = (int)(b.hdr[t].nslots & 0xFFu), ch = (int)((b.hdr[t].nslots >> 8) & 0xFFu);
+            const uint32_t S = b.hdr[t].stride & ((1u << kStrideBits) - 1);
+            const TileSlot* ts = b.slots.data() + (size_t)t * kTileSlots;
             int k = 0;
             while (k + 1 < n_bins && ch >= edges[k + 1]) k++;
             hist[k]++;
             uint32_t lds = kTileZeroDwords;
-            for (int j = 0; j < (int)(b.hdr[t].nslots & 0xFFu); j++)
-                lds += (b.hdr[t].stride & ((1u << kStrideBits) - 1)) * b.slots[(size_t)t * kTileSlots + j].bh;
+            bool late = false, early = false;
+            for (int j = 0; j < ns; j++) {
+                lds += S * ts[j].bh;
+                late |= j > 0 && ts[j].chunk0 >= kGroupFirst;
+                early |= j > 0 && ts[j].chunk0 < kGroupFirst && ch > kGroupFirst;
+            }
+            by_slots[std::min(ns, kTileSlots)]++;
+            late_slot += late;
+            early_slot += early;
+            overflow += ch > kGroupFirst;
+            max_chunks = std::max(max_chunks, (uint32_t)ch);
+            max_stride = std::max(max_stride, S);
+            max_lds = std::max(max_lds, lds * 4u);
             const uint32_t kb = lds * 4u / 1024u;  // 0-1, 1-2, 2-4, 4-8, 8-16, 16-24, >24 KiB
             lds_hist[kb < 1 ? 0 : kb < 2 ? 1 : kb < 4 ? 2 : kb < 8 ? 3 : kb < 16 ? 4 : kb < 24 ? 5 : 6]++;
             for (int g = 0; g < kStitchBands; g++)
@@ -405,6 +431,19 @@ TiledLutBuild build_tiled_lut(const std::vector<TileJob>& jobs, const EntryFn& e
             b.n_packable += b.packable[t];
         }
         s += ", \"items_packable\": " + std::to_string(b.n_packable);
+        s += ", \"items_by_slots\": [";
+        for (int k = 0; k <= kTileSlots; k++) s += (k ? ", " : "") + std::to_string(by_slots[k]);
+        s += "]";
+        const std::pair<const char*, size_t> counts[] = {{"max_chunks", max_chunks},
+                                                          {"max_lds_bytes", max_lds},
+                                                          {"max_stride", max_stride},
+                                                          {"grp1_chunks", b.grp1.size() / 64},
+                                                          {"items_overflow", (size_t)overflow},
+                                                          {"items_late_slot", (size_t)late_slot},
+                                                          {"items_early_slot", (size_t)early_slot},
+                                                          {"black_groups", black_groups},
+                                                          {"grp1_black_groups", black_groups1}};
+        for (const auto& c : counts) s += std::string(", \"") + c.first + "\": " + std::to_string(c.second);
         b.stats = s;
     }
     b.hdr.resize(std::max(n_items, 1));

@@ -63,6 +63,7 @@ _lib.octvr_rig_num_overlays.argtypes = [_VP, C.POINTER(C.c_int)]
 _lib.octvr_rig_get_overlay.argtypes = [_VP, C.c_int, C.POINTER(InputView)]
 _lib.octvr_rig_morph_controlpoints.argtypes = [_VP, C.c_char_p, C.POINTER(C.c_int)]
 _lib.octvr_rig_get_triangles.argtypes = [_VP, C.c_int, _VP, _VP, C.c_int, C.POINTER(C.c_int)]
+_lib.octvr_rig_set_vignette.argtypes = [_VP, C.c_int, C.c_int, _VP, C.c_int, C.c_int]
 _lib.octvr_rig_destroy.argtypes = [_VP]
 _lib.octvr_rig_destroy.restype = None
 _lib.octvr_mapper_create.argtypes = [_VP, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int,
@@ -476,6 +477,16 @@ class MapperTemplate:
         k = v.vignette_w * v.vignette_h
         return np.ctypeslib.as_array(C.cast(v.vignette, C.POINTER(C.c_float)), shape=(k,)).copy().reshape(
             v.vignette_h, v.vignette_w)
+
+    def set_vignette(self, i, gain_map):
+        """Sets input i's vignette map (octvr_rig_set_vignette): a 2-D float32 array of gains, resized to the
+        camera's size by the mappers created afterwards; None removes it."""
+        if gain_map is None:
+            _check(_lib.octvr_rig_set_vignette(self._h, int(i), 0, None, 0, 0))
+            return
+        a = np.ascontiguousarray(gain_map, np.float32)
+        assert a.ndim == 2
+        _check(_lib.octvr_rig_set_vignette(self._h, int(i), 0, a.ctypes.data_as(_VP), a.shape[1], a.shape[0]))
 
     def close(self):
         if self._h and self._h.value:

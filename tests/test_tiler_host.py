@@ -80,6 +80,14 @@ def test_tiled_lut_c2(product_lib):
     # every item fits the 16 KiB tile LDS; no item needs more than 4 staging chunks
     assert info["items_by_lds_kib"][5:] == [0, 0]
     assert sum(v for k, v in info["items_by_chunks"].items() if int(k) > 4) == 0
+    # the same from the per-item maxima (tests/test_tile_limits_host.py holds the cases that do go further); the
+    # whole string fits the 4096-byte buffer of debug_tiled_lut_info with room for Mapper.info()'s own keys
+    assert info["max_chunks"] <= 4 and info["grp1_chunks"] == 0 and info["items_overflow"] == 0
+    assert info["items_late_slot"] == 0 and info["items_early_slot"] == 0
+    assert sum(info["items_by_slots"]) == info["items"] and info["items_by_slots"][0] == 0
+    assert 0 < info["max_lds_bytes"] <= 16 * 1024 - 176 and 0 < info["max_stride"] <= 256 + 28
+    import json
+    assert len(json.dumps(info)) < 2048
     # the texture convention stages the same rig with one more column / row of taps per cell at most
     tex = ox.debug_tiled_lut_info(mt, sizes, remap="texture")
     assert tex["tex"] == 1 and tex["items"] + tex["wide_tiles"] // 2 == info["items"]
