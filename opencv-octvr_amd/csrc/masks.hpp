@@ -4,10 +4,9 @@
 #include <cstdint>
 #include <vector>
 
-namespace octvr {
+#include "fill_poly.hpp"  // fill_poly_u8: the polygonal areas
 
-// cv::fillPoly(img, {pts}, color) on a w x h CV_8U image, lineType 8, shift 0; pts = x0,y0,x1,y1,...
-void fill_poly_u8(uint8_t* img, int w, int h, const int* pts, int npts, uint8_t color);
+namespace octvr {
 
 // cv::imdecode(png, IMREAD_COLOR) restricted to PNG; returns w*h*3 bytes in R,G,B order.
 // expect_w > 0: the image must be expect_w x expect_h (checked on the IHDR, before inflating)

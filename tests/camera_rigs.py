@@ -130,15 +130,18 @@ def morph_rig(with_equirect=False):
     return {"output": {"type": "equirectangular", "options": {}}, "inputs": ins}
 
 
-def morph_points(luts, per_pair=5, seed=0, jitter=0.003):
+def morph_points(luts, per_pair=5, seed=0, jitter=0.003, pairs=None, region=None):
     """Control points [n0, n1, x0, y0, x1, y1]: output pixels seen by both cameras of a pair, camera
-    n0's point read from its map, camera n1's jittered by up to `jitter` (normalized input units)."""
+    n0's point read from its map, camera n1's jittered by up to `jitter` (normalized input units).
+    pairs: only these (n0, n1); region(X, Y) -> bool: only output pixels it accepts."""
     import numpy as np
     rng = np.random.default_rng(seed)
     n = len(luts)
     cps = []
     for a in range(n):
         for b in range(a + 1, n):
+            if pairs is not None and (a, b) not in pairs:
+                continue
             (ax, ay, aw, ah), a1, a2, am = luts[a]
             (bx, by, bw, bh), b1, b2, bm = luts[b]
             x0, y0 = max(ax, bx), max(ay, by)
@@ -146,6 +149,9 @@ def morph_points(luts, per_pair=5, seed=0, jitter=0.003):
             if x0 >= x1 or y0 >= y1:
                 continue
             both = (am[y0 - ay:y1 - ay, x0 - ax:x1 - ax] > 0) & (bm[y0 - by:y1 - by, x0 - bx:x1 - bx] > 0)
+            if region is not None:
+                gy, gx = np.mgrid[y0:y1, x0:x1]
+                both &= region(gx, gy)
             ys, xs = np.nonzero(both)
             if len(ys) < per_pair:
                 continue
