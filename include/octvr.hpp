@@ -657,6 +657,12 @@ public:
     // OCTVR_PIX_YUYV422 likewise; OCTVR_PIX_YUV422P takes Y (W x H), U and V (W/2 x H each), OCTVR_PIX_NV16 Y and
     // the U,V plane (CV_8UC1 of W x H or CV_8UC2 of W/2 x H); push_device takes whole frames of the layout.
     virtual void set_pixel_formats(int in_format, int out_format) = 0;
+    // Not in the reference: the layout of the merged frame, any OCTVR_PIX_* value (octvr_hip.h
+    // octvr_async_set_output_format; set_pixel_formats refuses the converted layouts as the output format).  With a
+    // converted layout the output tuple of push holds the layout's planes as the input side lays them out — the
+    // packed plane (CV_8UC1 of 2W x H) alone; Y and the U,V plane; or Y, U and V — 16-bit layouts as CV_16UC1 or as
+    // their bytes, and push_device's out is one device frame of the layout.  Every region must start at even x and y.
+    virtual void set_output_format(int out_format) = 0;
     // Not in the reference: the formats in use.
     virtual void pixel_formats(int& in_format, int& out_format) const = 0;
     // Not in the reference: the latest published preview (CV_8UC3, preview_size) and its header; false
@@ -749,6 +755,7 @@ public:
     void set_pixel_formats(int in_format, int out_format) override {
         check(octvr_async_set_pixel_formats(a_, in_format, out_format));
     }
+    void set_output_format(int out_format) override { check(octvr_async_set_output_format(a_, out_format)); }
     void pixel_formats(int& in_format, int& out_format) const override {
         check(octvr_async_pixel_formats(a_, &in_format, &out_format));
     }

@@ -439,6 +439,8 @@ int octvr_async_set_preview_sink(octvr_async* async, octvr_preview_sink sink, vo
  * run gaps included), runs, frame bytes, preview size, the mappers' creation flags, and "pixel_formats":
  * [in, out], the current OCTVR_PIX_* pair; "device_frames", the frames octvr_async_push_device has queued so
  * far, and "merge_launches", the merge kernel's launches for them (0 or 1 per device frame);
+ * "merge_pack_launches", merge_pack_kernel's launches (octvr_async_set_output_format: 1 per frame of a converted
+ * output layout, host and device frames alike, else 0);
  * "preview_prepared": per mapper the [w, h] of the preview it gathers from the source frames ([0, 0]: none). */
 int octvr_async_info(const octvr_async* async, char* buf, size_t len);
 /* Pixel layouts of the pipeline's host planes (no reference counterpart: the reference's planes are planar;
@@ -465,22 +467,62 @@ int octvr_async_info(const octvr_async* async, char* buf, size_t len);
  * takes one packed device frame per camera (pitch >= 2 W).  The copy-in packs the footprint runs of the packed
  * rows at 2 B per pixel, and one kernel converts them — a device frame's straight from the caller's frames,
  * after ready_event — into NV12 device frames that all mappers read (they stay on NV12 input: one conversion
- * per frame, not one per mapper).  As the output format it is OCTVR_E_UNSUPPORTED: the merge, the copy-out
- * and the registered planes are per-plane tables of a 4:2:0 frame.
+ * per frame, not one per mapper).  As the output format of this call it is OCTVR_E_UNSUPPORTED: the merge, the
+ * copy-out and the registered planes it sets up are per-plane tables of a 4:2:0 frame; the merged frame in a
+ * converted layout is octvr_async_set_output_format's.
  * OCTVR_PIX_YUYV422, OCTVR_PIX_YUV422P and OCTVR_PIX_NV16 are valid as the input format in the same way (one
- * conversion per frame for all mappers), and OCTVR_E_UNSUPPORTED as the output format for the same reason.  Host
+ * conversion per frame for all mappers), and OCTVR_E_UNSUPPORTED as the output format here for the same reason.  Host
  * planes of a push: YUYV in_planes[3*i] only (2 W bytes x H rows); YUV422P Y (W x H), U and V (W/2 bytes x H rows
  * each); NV16 Y and the U,V plane (W bytes x H rows each), the third entry is ignored.  The copy-in packs a
  * footprint run at 4 bytes per pixel of the run: its two luma rows, then its two chroma rows in the format's
  * layout.  octvr_async_push_device takes one device frame per camera in the Mapper's layout of the format.
- * OCTVR_PIX_P010, OCTVR_PIX_YUV420P10, OCTVR_PIX_P210 and OCTVR_PIX_YUV422P10 likewise: input only (as the output
- * format OCTVR_E_UNSUPPORTED, nothing changed).  Host planes of a push, rows of 16-bit words with even pitches and
+ * OCTVR_PIX_P010, OCTVR_PIX_YUV420P10, OCTVR_PIX_P210 and OCTVR_PIX_YUV422P10 likewise: the input format only here (as
+ * the output format OCTVR_E_UNSUPPORTED, nothing changed; octvr_async_set_output_format sets them).  Host planes of a push, rows of 16-bit words with even pitches and
  * addresses: P010 / P210 Y (2 W bytes x H rows) and the U,V plane (2 W bytes x H/2 or H rows), the third entry is
  * ignored; the planar two Y, U and V (U and V W bytes x H/2 or H rows each).  The copy-in packs a footprint run as
  * its two luma rows, then its chroma row(s) in the format's layout: 6 bytes per pixel of the run for 4:2:0, 8 for
  * 4:2:2.  octvr_async_push_device takes one device frame per camera in the Mapper's layout of the format. */
 int octvr_async_set_pixel_formats(octvr_async* async, int in_format, int out_format);
 int octvr_async_pixel_formats(const octvr_async* async, int* in_format, int* out_format);
+/* The layout of the merged frame, any of the ten OCTVR_PIX_* values (no reference counterpart: a playout card
+ * takes UYVY or YUYV, a Main10 encoder P010).  For OCTVR_PIX_YUV420P and OCTVR_PIX_NV12 this is
+ * octvr_async_set_pixel_formats(current input format, out_format).  For a converted layout D (UYVY422, YUYV422,
+ * YUV422P, NV16, P010, YUV420P10, P210, YUV422P10) the input format stays as it is, every mapper is put on NV12
+ * output, and one kernel per frame (merge_pack_kernel) reads the mappers' NV12 region frames and writes the merged
+ * frame in layout D: the merge and the out rule of octvr_mapper_set_pixel_formats in one pass, with no merged
+ * 4:2:0 intermediate.  octvr_async_pixel_formats and octvr_async_info's "pixel_formats" then report D as the output
+ * format; "merge_pack_launches" counts the kernel's launches, one per frame, host and device frames alike (a device
+ * frame's single whole-frame region is not stitched in place with a converted output).
+ *   Region rule: a region must be a whole sub-picture of the layout.  With r and c the luma and chroma rectangles
+ *     octvr_async_create computed, r.x and r.y are even, c.x == r.x / 2 and c.y == r.y / 2 for every region;
+ *     otherwise OCTVR_E_INVALID, naming the region, with nothing changed.  (Creation keeps its looser rule: the
+ *     planar outputs place luma and chroma independently, a pixel pair of a packed row cannot.)
+ *   The merged frame is D's row bytes of out_w wide and D's rows of out_h high (the table under
+ *     octvr_mapper_set_pixel_formats); the pitch is at least a row; for 16-bit layouts bases and pitches are even;
+ *     a device frame is below 2 GiB.  octvr_async_push and octvr_async_register_output take D's host planes as the
+ *     input side lays them out: one packed plane (2 out_w bytes x out_h rows); Y and the U,V plane; or Y, U and V
+ *     (each half a row's bytes wide), chroma planes of out_h / 2 rows (4:2:0) or out_h rows (4:2:2); entries past the
+ *     layout's planes are ignored.  octvr_async_push_device takes out_dev / out_pitch as one device frame in the
+ *     Mapper's layout of D.
+ *   Where region k lands (S = bytes per sample, cr = chroma rows per row pair, 1 or 2):
+ *     packed   rows [r.y, r.y + r.h), bytes [2 r.x, 2 r.x + 2 r.w);
+ *     pairs    luma rows [r.y, r.y + r.h), bytes [S r.x, S (r.x + r.w)); chroma rows out_h + cr r.y / 2 +
+ *              [0, cr r.h / 2) of a frame (rows cr r.y / 2 + [0, cr r.h / 2) of the U,V plane), the same bytes;
+ *     halves   luma as pairs; the same chroma rows, U at bytes [S r.x / 2, S (r.x + r.w) / 2) and V at
+ *              S out_w / 2 plus the same in a frame (at the same bytes of the V plane).
+ *   The bytes are the out rule applied to the bytes the same pipeline writes there with NV12 output, bit for bit:
+ *     10-bit samples are v8 << 8 (bits 15..6) or v8 << 2 (bits 9..0), the other bits 0; with 4:2:2 each chroma row
+ *     is written twice.  Bytes outside every region, and between a row's width and its pitch, are never written, in
+ *     device frames, host planes and registered planes.  Preview, gain chaining, overlays and pop order are
+ *     untouched.
+ *   A host frame: each slot owns one device frame of layout D, which the same launch fills; each region's plane
+ *     rectangles are downloaded by one 2-D copy each, straight into registered planes or into pinned staging, whose
+ *     rows the copy-out then copies.  These buffers are allocated by this call and freed when a later
+ *     octvr_async_set_pixel_formats(in, native out) leaves converted output — which is also how the input format is
+ *     changed while the output is converted: set the pair, then call this again.
+ * OCTVR_E_INVALID, nothing changed: an unknown value; frames pending; a change of the output format while output
+ * plane sets are registered; the region rule; more than 32 regions.  Synchronizes. */
+int octvr_async_set_output_format(octvr_async* async, int out_format);
 /* push(inputs, output) (async.cpp:174-189): in_planes[3*i+0/1/2] = Y, U, V host planes of input i
  * (W x H, W/2 x H/2, W/2 x H/2) with row pitches in_pitches[3*i+k]; out_planes[0/1/2] / out_pitches: the
  * merged output's Y (out_w x out_h), U and V (out_w/2 x out_h/2) planes (NV12 sides: Y, U,V, unused — see

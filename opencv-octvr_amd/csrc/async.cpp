@@ -32,11 +32,14 @@
 //   * the inputs may be in a converted capture layout (frame_layout.hpp: packed UYVY 4:2:2, what capture cards
 //     deliver, YUYV, YUV422P, NV16 and the 10-bit P010, YUV420P10, P210, YUV422P10): one kernel (frame_layout.hip)
 //     converts the uploaded runs into the slot's NV12 device frames — once for all mappers, which stay on NV12
-//     input; device frames are converted the same way from the caller's frames.
+//     input; device frames are converted the same way from the caller's frames;
+//   * the merged frame may be in a converted layout too (octvr_async_set_output_format): the mappers write NV12
+//     region frames and one kernel (async_merge_pack.hip) merges and converts them in one pass, into the caller's
+//     device frame or into the slot's own frame of that layout, whose region rectangles are then downloaded.
 // Every input layout takes the same host path: a table of footprint runs with their places in the packed buffer
 // (RunPlan: the native layouts' at 3 B per pixel of a run's row, a converted layout's run_table at 4, 6 or 8), one
 // pack_run per run, one upload, one unpack launch.  Every output path places a region's pieces by one table
-// (async_host.hpp region_pieces).
+// (async_host.hpp region_pieces; a converted output layout's by region_rects).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -132,6 +135,10 @@ struct Slot {  // one frame's buffers: the packed footprint runs, the device fra
     std::vector<std::unique_ptr<PinnedBuf>> out_host;
     std::vector<DevBuf<uint8_t>> in_dev, out_dev;
     FootFrames frames{};
+    // with a converted output layout (octvr_async_set_output_format): the merged frame of that layout, pitch = its
+    // row bytes, which merge_pack_kernel fills for a host frame, and the pinned staging of its region rectangles
+    std::unique_ptr<DevBuf<uint8_t>> conv_out_dev;
+    std::unique_ptr<PinnedBuf> conv_out_host;
 };
 
 struct Job {
@@ -317,6 +324,17 @@ struct octvr_async {
     int pending = 0;  // pushed, not popped (caller thread only)
     int64_t device_frames = 0;               // octvr_async_push_device calls that queued a frame (caller thread only)
     std::atomic<int64_t> merge_launches{0};  // merge_regions_kernel launches (compute thread)
+    std::atomic<int64_t> merge_pack_launches{0};  // merge_pack_kernel launches (compute thread)
+    // a converted output layout (octvr_async_set_output_format): out_fmt is that layout, the mappers write NV12
+    bool out_conv() const { return converted_format(out_fmt); }
+    size_t conv_out_pitch() const { return (size_t)layout_of(out_fmt).row_bytes(out_w); }
+    LayoutRects rects(size_t k) const { return region_rects(layout_of(out_fmt), regions[k], out_w, out_h); }
+    void free_conv_out() {
+        for (auto& sl : slots) {
+            sl.conv_out_dev.reset();
+            sl.conv_out_host.reset();
+        }
+    }
     RegionPieces pieces(size_t k) const { return region_pieces(regions[k], regions_uv[k], out_fmt == OCTVR_PIX_NV12); }
     bool whole_frame_region() const {
         return regions.size() == 1 && regions[0].x == 0 && regions[0].y == 0 && regions[0].w == out_w && regions[0].h == out_h;
@@ -340,6 +358,8 @@ struct octvr_async {
             sl.preview_dev.reset();
             sl.preview_host.reset();
             sl.out_host.clear();
+            sl.conv_out_dev.reset();
+            sl.conv_out_host.reset();
         }
         for (auto* m : mappers) octvr_mapper_destroy(m);
         if (prev >= 0) (void)hipSetDevice(prev);
@@ -406,7 +426,7 @@ struct octvr_async {
                 conv_unpack(src, sl.frames, comp);
             }
             // a device frame's single region covering the whole output is stitched where it belongs
-            const bool in_place = j.device && whole_frame_region();
+            const bool in_place = j.device && !out_conv() && whole_frame_region();
             for (size_t k = 0; k < mappers.size(); k++) {
                 const int gm = gain_modes[k];
                 const double* chained = nullptr;
@@ -424,7 +444,16 @@ struct octvr_async {
                               in_place ? j.out_pitch : (size_t)regions[k].w, nullptr, 0, chained, comp,
                               with_pv ? &pv : nullptr);
             }
-            if (j.device && !in_place) {  // every region frame into its place in the merged frame, one launch
+            if (out_conv()) {  // every NV12 region frame into the merged frame of the output layout, one launch
+                std::vector<const uint8_t*> src;
+                for (auto& b : sl.out_dev) src.push_back(b.p);
+                MergePackTable t;
+                REQUIRE(build_merge_pack_table(layout_of(out_fmt), regions.data(), regions_uv.data(), src.data(), (int)src.size(),
+                                               out_w, out_h, j.device ? j.out_pitch : conv_out_pitch(), t),
+                        "regions do not fit a merge launch");
+                HIP_CHECK(launch_merge_pack(out_fmt, j.device ? j.out_dev : sl.conv_out_dev->p, t, comp));
+                merge_pack_launches++;
+            } else if (j.device && !in_place) {  // every region frame into its place in the merged frame, one launch
                 std::vector<const uint8_t*> src;
                 for (auto& b : sl.out_dev) src.push_back(b.p);
                 MergeTable t;
@@ -444,6 +473,21 @@ struct octvr_async {
             DeviceGuard dg(device);
             Slot& sl = slots[j.slot];
             for (size_t k = 0; k < mappers.size() && !j.device; k++) {
+                if (out_conv()) {
+                    // the region's rectangles of the slot's merged frame: into the caller's registered planes, or
+                    // to the same place in the pinned staging
+                    const size_t fp = conv_out_pitch();
+                    const LayoutRects rc = rects(k);
+                    for (int i = 0; i < rc.n; i++) {
+                        const LayoutRect& p = rc.p[i];
+                        const size_t at = p.fy * fp + p.fx;
+                        uint8_t* const dst = j.direct ? j.out_planes[p.plane] + p.y * j.out_pitches[p.plane] + p.x
+                                                      : sl.conv_out_host->p + at;
+                        HIP_CHECK(hipMemcpy2DAsync(dst, j.direct ? j.out_pitches[p.plane] : fp, sl.conv_out_dev->p + at, fp, p.bytes,
+                                                   p.rows, hipMemcpyDeviceToHost, down));
+                    }
+                    continue;
+                }
                 if (!j.direct) {
                     HIP_CHECK(hipMemcpyAsync(sl.out_host[k]->p, sl.out_dev[k].p, sl.out_host[k]->n, hipMemcpyDeviceToHost,
                                              down));
@@ -471,7 +515,22 @@ struct octvr_async {
         stage(j, [&] {
             if (j.direct || j.device) return;  // the D2H wrote the caller's planes / the frame stays on the device
             Slot& sl = slots[j.slot];
-            for (size_t k = 0; k < mappers.size(); k++) {
+            for (size_t k = 0; k < mappers.size() && out_conv(); k++) {
+                // the rows of the region's rectangles, plane after plane, split over the pool
+                const size_t fp = conv_out_pitch();
+                const LayoutRects rc = rects(k);
+                size_t first[4] = {0, 0, 0, 0};
+                for (int i = 0; i < rc.n; i++) first[i + 1] = first[i] + rc.p[i].rows;
+                copy_out_pool.run(first[rc.n], [&](size_t lo, size_t hi) {
+                    for (int i = 0; i < rc.n; i++) {
+                        const LayoutRect& p = rc.p[i];
+                        for (size_t y = std::max(lo, first[i]); y < std::min(hi, first[i + 1]); y++)
+                            memcpy(j.out_planes[p.plane] + (p.y + y - first[i]) * j.out_pitches[p.plane] + p.x,
+                                   sl.conv_out_host->p + (p.fy + y - first[i]) * fp + p.fx, p.bytes);
+                    }
+                });
+            }
+            for (size_t k = 0; k < mappers.size() && !out_conv(); k++) {
                 const RegionPieces pc = pieces(k);
                 const size_t w = (size_t)regions[k].w, luma_rows = pc.p[0].rows;
                 const uint8_t* src = sl.out_host[k]->p;
@@ -866,7 +925,8 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
             throw OctvrError(OCTVR_E_UNSUPPORTED,
                              "the converted layouts (4:2:2, 10-bit) are input formats of the pipeline only: its merge, copy-out "
                              "and registered output planes are per-plane tables of an 8-bit 4:2:0 frame (a Mapper writes them: "
-                             "octvr_mapper_set_pixel_formats)");
+                             "octvr_mapper_set_pixel_formats; the pipeline's merged frame in such a layout is "
+                             "octvr_async_set_output_format's)");
         REQUIRE(a->pending == 0, "frames pending: pop them before changing the pixel formats");
         REQUIRE(out_format == a->out_fmt || a->reg_out.empty(),
                 "output planes are registered: unregister them before changing the output format");
@@ -905,6 +965,58 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
                     HIP_CHECK(hipMemset(sl.in_dev[i].p, 0x5A, (size_t)a->in_w[i] * (a->in_h[i] / 2 * 3)));
         }
         a->in_fmt = in_format;
+        a->out_fmt = out_format;
+        a->free_conv_out();  // a native output format leaves converted output
+    }, OCTVR_E_HIP);
+}
+
+int octvr_async_set_output_format(octvr_async* a, int out_format) {
+    if (!a) {
+        set_last_error("NULL argument");
+        return OCTVR_E_INVALID;
+    }
+    if (out_format == OCTVR_PIX_YUV420P || out_format == OCTVR_PIX_NV12)
+        return octvr_async_set_pixel_formats(a, a->in_fmt, out_format);
+    return guarded([&] {
+        const LayoutDesc d = layout_of(out_format);
+        REQUIRE(d.converted(), "pixel format must be an OCTVR_PIX_* value");
+        REQUIRE(a->pending == 0, "frames pending: pop them before changing the output format");
+        REQUIRE(out_format == a->out_fmt || a->reg_out.empty(),
+                "output planes are registered: unregister them before changing the output format");
+        REQUIRE((int)a->regions.size() <= kMergeMaxRegions, "more regions than one merge launch takes");
+        for (size_t k = 0; k < a->regions.size(); k++)
+            if (!region_is_subpicture(a->regions[k], a->regions_uv[k]))
+                throw OctvrError(OCTVR_E_INVALID, "output region " + std::to_string(k) +
+                                                      " is no whole sub-picture of a converted layout: its x and y must be even "
+                                                      "and its chroma rectangle must start at their halves");
+        const size_t pitch = (size_t)d.row_bytes(a->out_w), bytes = pitch * (size_t)d.rows(a->out_h);
+        {
+            std::vector<const uint8_t*> src(a->regions.size(), nullptr);
+            MergePackTable t;
+            REQUIRE(build_merge_pack_table(d, a->regions.data(), a->regions_uv.data(), src.data(), (int)src.size(), a->out_w,
+                                           a->out_h, pitch, t),
+                    "the merged frame of this layout does not fit a merge launch (2 GiB, 2^31 work items)");
+        }
+        DeviceGuard dg(a->device);
+        // the slots' merged frame and its staging first: a failed allocation leaves the formats as they were
+        std::vector<std::unique_ptr<DevBuf<uint8_t>>> dev(kSlots);
+        std::vector<std::unique_ptr<PinnedBuf>> host(kSlots);
+        for (int s = 0; s < kSlots; s++) {
+            dev[s].reset(new DevBuf<uint8_t>());
+            dev[s]->alloc(bytes);
+            host[s].reset(new PinnedBuf());
+            host[s]->alloc(bytes);
+        }
+        // the mappers keep their input format and write NV12 region frames, the frame pack_lane reads
+        const int mapper_in = a->in_conv() ? OCTVR_PIX_NV12 : a->in_fmt;
+        for (octvr_mapper* m : a->mappers) {
+            const int rc = octvr_mapper_set_pixel_formats(m, mapper_in, OCTVR_PIX_NV12);
+            if (rc != OCTVR_OK) throw OctvrError(rc, octvr_last_error());
+        }
+        for (int s = 0; s < kSlots; s++) {
+            a->slots[s].conv_out_dev = std::move(dev[s]);
+            a->slots[s].conv_out_host = std::move(host[s]);
+        }
         a->out_fmt = out_format;
     }, OCTVR_E_HIP);
 }
@@ -956,14 +1068,14 @@ int octvr_async_info(const octvr_async* a, char* buf, size_t len) {
     size_t in_bytes = 0, out_bytes = 0;
     for (int i = 0; i < a->n_in; i++) in_bytes += (size_t)a->in_w[i] * (a->in_h[i] / 2 * 3);
     for (const Rect& r : a->regions) out_bytes += (size_t)r.w * (r.h / 2 * 3);
-    char tmp[768];
+    char tmp[1024];
     snprintf(tmp, sizeof tmp,
              "{\"mappers\": %d, \"inputs\": %d, \"packed_bytes\": %zu, \"runs\": %zu, \"input_frame_bytes\": %zu, "
              "\"output_bytes\": %zu, \"preview\": [%d, %d], \"flags\": %d, \"slots\": %d, \"pixel_formats\": [%d, %d], "
-             "\"device_frames\": %lld, \"merge_launches\": %lld",
+             "\"device_frames\": %lld, \"merge_launches\": %lld, \"merge_pack_launches\": %lld",
              (int)a->mappers.size(), a->n_in, a->native.bytes, a->native.runs.size(), in_bytes, out_bytes, a->preview_w,
              a->preview_h, a->flags, kSlots, a->in_fmt, a->out_fmt, (long long)a->device_frames,
-             (long long)a->merge_launches.load());
+             (long long)a->merge_launches.load(), (long long)a->merge_pack_launches.load());
     // per mapper the preview size it gathers from the source frames ([0, 0]: it previews from its result frame,
     // or has no preview)
     std::string js = tmp;

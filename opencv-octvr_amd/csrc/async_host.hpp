@@ -2,8 +2,9 @@
 // the merge of the output planes' byte ranges before they are page-locked (octvr_async_register_output), where
 // the pieces of a region frame land in the output planes (region_pieces: the D2H copies, the copy-out and the
 // merge table all place them by it), and the region table and work-item arithmetic of the device-frame merge
-// (octvr_async_push_device), which merge_regions_kernel shares.  The input side (the layouts' planes, pack_run)
-// is frame_layout.hpp's.
+// (octvr_async_push_device), which merge_regions_kernel shares; and for a merged frame in a converted layout
+// (octvr_async_set_output_format) the region rule, a region's rectangles per plane (region_rects) and the table and
+// work items merge_pack_kernel shares.  The input side (the layouts' planes, pack_run) is frame_layout.hpp's.
 #pragma once
 
 #include <algorithm>
@@ -187,6 +188,110 @@ OCTVR_LAYOUT_HD inline MergeSpan merge_item(const MergeTable& t, uint32_t id, ui
     if (chunk == 0) return MergeSpan{s, d, c.head};
     if (c.b0 >= n) return MergeSpan{s, d, 0};
     return MergeSpan{s + c.b0, d + (size_t)c.b0, c.len(n)};
+}
+
+// ---- the merged frame in a converted layout (octvr_async_set_output_format, async_merge_pack.hip) -------------
+// With a converted output layout D the mappers write NV12 region frames and one launch of merge_pack_kernel<D>
+// writes every region into the merged frame of layout D: frame_layout.hpp's out rule (pack_lane) per region, the
+// region a sub-picture of the frame (pack_item_at).
+
+// A region must be a whole sub-picture of the layout: a pixel pair of a packed row, a U,V pair and a chroma row
+// cannot be split, so the luma origin is even and the chroma origin is its half (creation's looser rule places
+// luma and chroma independently).
+inline bool region_is_subpicture(const PlaneRect& r, const PlaneRect& c) {
+    return (r.x & 1) == 0 && (r.y & 1) == 0 && c.x == r.x / 2 && c.y == r.y / 2;
+}
+
+// The rectangles of region r (its luma rectangle; region_is_subpicture) in the planes of layout d, the converted
+// counterpart of region_pieces: `bytes` bytes of `rows` rows at byte column x, row y of host plane `plane` (one
+// packed plane; Y and the U,V plane; or Y, U and V), which in the one-piece frame of an out_w x out_h picture (the
+// Mapper's layout of d: a device frame, the slots' staging) is byte column fx of row fy.  The download, the
+// copy-out, the kernel's table and the CPU check all place a region by it.
+struct LayoutRect {
+    int plane;
+    size_t x, y, bytes, rows;
+    size_t fx, fy;
+};
+struct LayoutRects {
+    int n;  // d.planes()
+    LayoutRect p[3];  // the luma (packed) rectangle first
+};
+inline LayoutRects region_rects(const LayoutDesc& d, const PlaneRect& r, int out_w, int out_h) {
+    const size_t S = (size_t)d.bytes, x = (size_t)r.x, y = (size_t)r.y, w = (size_t)r.w, h = (size_t)r.h;
+    LayoutRects o{d.planes(), {{}, {}, {}}};
+    if (d.packed()) {
+        o.p[0] = LayoutRect{0, 2 * x, y, 2 * w, h, 2 * x, y};
+        return o;
+    }
+    const size_t cr = (size_t)d.chroma_rows, cy = cr * (y / 2), ch = cr * (h / 2);
+    o.p[0] = LayoutRect{0, S * x, y, S * w, h, S * x, y};
+    if (!d.halves()) {
+        o.p[1] = LayoutRect{1, S * x, cy, S * w, ch, S * x, (size_t)out_h + cy};
+    } else {
+        o.p[1] = LayoutRect{1, S * x / 2, cy, S * w / 2, ch, S * x / 2, (size_t)out_h + cy};
+        o.p[2] = LayoutRect{2, S * x / 2, cy, S * w / 2, ch, S * (size_t)out_w / 2 + S * x / 2, (size_t)out_h + cy};
+    }
+    return o;
+}
+
+// One region of a merge_pack launch; src is the mapper's NV12 region frame (pitch = w).
+struct MergePackRegion {
+    const uint8_t* src;
+    int w, h;
+    uint32_t y_off, u_off, v_off;  // PackPlace of the region in the merged frame
+    uint32_t first;                // index of the region's first work item
+};
+struct MergePackTable {
+    uint32_t pitch;  // of the merged frame
+    int n;
+    uint32_t items;
+    MergePackRegion r[kMergeMaxRegions];
+};
+
+// The table for regions r / c (octvr_async_create's rectangles) of an out_w x out_h merged frame of layout d at
+// `pitch`.  false: no converted layout, more than kMergeMaxRegions regions, a rectangle outside the frame, a region
+// that is no sub-picture, a pitch below a row, 2^31 - 1 work items or more, or a frame of 2 GiB or more.
+inline bool build_merge_pack_table(const LayoutDesc& d, const PlaneRect* r, const PlaneRect* c, const uint8_t* const* src, int n,
+                                   int out_w, int out_h, size_t pitch, MergePackTable& t) {
+    if (!d.converted() || n <= 0 || n > kMergeMaxRegions || out_w <= 0 || out_h <= 0 || (out_w & 1) || (out_h & 1)) return false;
+    if (pitch < (size_t)d.row_bytes(out_w)) return false;
+    if ((uint64_t)pitch * (uint64_t)d.rows(out_h) >= 0x7FFFFF80ull) return false;
+    t.pitch = (uint32_t)pitch;
+    t.n = n;
+    uint64_t items = 0;
+    for (int k = 0; k < n; k++) {
+        const PlaneRect &a = r[k], &b = c[k];
+        if (a.x < 0 || a.y < 0 || a.w <= 0 || a.h <= 0 || (a.w & 1) || (a.h & 1) || a.x + a.w > out_w || a.y + a.h > out_h)
+            return false;
+        if (b.w != a.w / 2 || b.h != a.h / 2 || !region_is_subpicture(a, b)) return false;
+        const LayoutRects rc = region_rects(d, a, out_w, out_h);
+        auto off = [&](const LayoutRect& p) { return (uint32_t)(p.fy * pitch + p.fx); };
+        MergePackRegion& m = t.r[k];
+        m.src = src[k];
+        m.w = a.w;
+        m.h = a.h;
+        m.y_off = off(rc.p[0]);
+        m.u_off = off(rc.p[rc.n > 1 ? 1 : 0]);
+        m.v_off = off(rc.p[rc.n - 1]);
+        m.first = (uint32_t)items;
+        items += pack_items(d, a.w, a.h);
+        if (items >= 0x7FFFFFFFull) return false;
+    }
+    for (int k = n; k < kMergeMaxRegions; k++) t.r[k] = MergePackRegion{nullptr, 0, 0, 0, 0, 0, (uint32_t)items};
+    t.items = (uint32_t)items;
+    return true;
+}
+
+// What work item `id` (< t.items) writes: the span of pack_item_at for its region, and the region in k; the
+// caller's lane is pack_lane(mem, t.r[k].src, out, t.r[k].w, t.r[k].h, span).  The region is found as merge_item
+// finds it, by the regions' first items.
+OCTVR_LAYOUT_HD inline LayoutSpan merge_pack_item(const LayoutDesc& d, const MergePackTable& t, uint32_t id, uintptr_t out_base,
+                                                  int& k) {
+    k = 0;
+    for (int i = 1; i < t.n; i++)
+        if (id >= t.r[i].first) k = i;
+    const MergePackRegion& m = t.r[k];
+    return pack_item_at(d, m.w, m.h, t.pitch, PackPlace{m.y_off, m.u_off, m.v_off}, out_base, id - m.first);
 }
 
 }  // namespace octvr

@@ -451,7 +451,19 @@ struct LayoutSpan {
     int row, n, b0, len;
     size_t dst;
 };
-OCTVR_LAYOUT_HD inline LayoutSpan pack_item(const LayoutDesc& d, int w, int h, size_t pitch, uintptr_t out_base, uint32_t id) {
+// Where the rows of a w x h picture start in the frame it is written to, as byte offsets from the frame's first
+// byte: y its first luma (packed) row; u its first chroma row (the halves kind: that row's U half); v the halves
+// kind's first V half.  The rows of each follow at the frame's pitch.  A picture that is the whole frame is
+// whole_frame_place; a sub-picture placed in a larger frame (the pipeline's merged frame: async_host.hpp
+// region_rects) has its own three offsets, and the list rows, their lengths and the chunks are the picture's own.
+struct PackPlace {
+    size_t y, u, v;
+};
+OCTVR_LAYOUT_HD inline PackPlace whole_frame_place(const LayoutDesc& d, int w, int h, size_t pitch) {
+    return PackPlace{0, (size_t)h * pitch, (size_t)h * pitch + (size_t)(d.row_bytes(w) / 2)};
+}
+OCTVR_LAYOUT_HD inline LayoutSpan pack_item_at(const LayoutDesc& d, int w, int h, size_t pitch, const PackPlace& at,
+                                               uintptr_t out_base, uint32_t id) {
     LayoutSpan sp{0, 0, 0, 0, 0};
     int chunk;
     const int n_full = d.row_bytes(w), full = full_rows(d, h);
@@ -462,14 +474,14 @@ OCTVR_LAYOUT_HD inline LayoutSpan pack_item(const LayoutDesc& d, int w, int h, s
         if (!d.halves() && sp.row >= full) return sp;
         chunk = (int)(id - (uint32_t)sp.row * per_full);
         sp.n = n_full;
-        sp.dst = (size_t)sp.row * pitch;
+        sp.dst = sp.row < h ? at.y + (size_t)sp.row * pitch : at.u + (size_t)(sp.row - h) * pitch;
     } else {
         const uint32_t q = (id - first_half) / per_half;
         if (q >= (uint32_t)half_rows(d, h)) return sp;
         chunk = (int)(id - first_half - q * per_half);
         sp.row = h + (int)q;
         sp.n = n_full / 2;
-        sp.dst = (size_t)(h + (int)(q >> 1)) * pitch + (size_t)((q & 1u) ? n_full / 2 : 0);
+        sp.dst = ((q & 1u) ? at.v : at.u) + (size_t)(q >> 1) * pitch;
     }
     const RowChunk c = row_chunk(out_base + sp.dst, sp.n, chunk);
     if (chunk == 0) {
@@ -481,6 +493,9 @@ OCTVR_LAYOUT_HD inline LayoutSpan pack_item(const LayoutDesc& d, int w, int h, s
     sp.len = c.len(sp.n);
     sp.dst += (size_t)c.b0;
     return sp;
+}
+OCTVR_LAYOUT_HD inline LayoutSpan pack_item(const LayoutDesc& d, int w, int h, size_t pitch, uintptr_t out_base, uint32_t id) {
+    return pack_item_at(d, w, h, pitch, whole_frame_place(d, w, h, pitch), out_base, id);
 }
 
 // Where sample i of list row `row` comes from in the NV12 frame (pitch = w); a packed row's samples are its bytes.

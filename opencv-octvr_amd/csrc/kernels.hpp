@@ -290,6 +290,10 @@ hipError_t launch_unpack_runs_layout(const uint8_t* packed, const FootRun* runs,
 // build_merge_table) into its place in the merged device frame `out`, one launch.
 struct MergeTable;
 hipError_t launch_merge_regions(uint8_t* out, const MergeTable& t, hipStream_t s);
+// octvr_async_set_output_format's merge (async_merge_pack.hip): every NV12 region frame of the table (async_host.hpp
+// build_merge_pack_table) into its place in the merged frame `out` of the converted layout `pix`, one launch.
+struct MergePackTable;
+hipError_t launch_merge_pack(int pix, uint8_t* out, const MergePackTable& t, hipStream_t s);
 // The converted capture layouts (the OCTVR_PIX_* values >= 16, frame_layout.hip; the arithmetic, the table and the
 // layouts' descriptors in frame_layout.hpp; `pix` is the OCTVR_PIX_* value).
 // launch_layout_unpack: the groups of the table's pieces (run_table: runs of at most 64 groups) from sources of the

@@ -143,6 +143,8 @@ _lib.octvr_async_pending.argtypes = [_VP, C.POINTER(C.c_int)]
 if hasattr(_lib, "octvr_async_set_pixel_formats"):  # (absent from older libraries OCTVR_HIP_LIB may select for an A/B)
     _lib.octvr_async_set_pixel_formats.argtypes = [_VP, C.c_int, C.c_int]
     _lib.octvr_async_pixel_formats.argtypes = [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+if hasattr(_lib, "octvr_async_set_output_format"):  # (absent from older libraries OCTVR_HIP_LIB may select for an A/B)
+    _lib.octvr_async_set_output_format.argtypes = [_VP, C.c_int]
 _lib.octvr_async_destroy.argtypes = [_VP]
 _lib.octvr_async_destroy.restype = None
 _lib.octvr_fill_poly_u8.argtypes = [_VP, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_uint8]
@@ -564,6 +566,19 @@ def frame_shape(fmt, w, h):
     if v in (PIX_YUV422P, PIX_NV16):
         return (2 * int(h), int(w))
     return (int(h) * 3 // 2, int(w))
+
+
+def plane_shapes(fmt, w, h):
+    """[(rows, bytes per row)] of the host planes of a w x h frame in `fmt`, as AsyncMultiMapper.push takes them: one
+    packed plane; Y and the U,V plane; or Y, U and V (each half a row's bytes wide)."""
+    v = _pix_value(fmt)
+    w, h, S = int(w), int(h), 2 if v in _PIX_10BIT else 1
+    if v in (PIX_UYVY422, PIX_YUYV422):
+        return [(h, 2 * w)]
+    ch = h // 2 if v in (PIX_YUV420P, PIX_NV12, PIX_P010, PIX_YUV420P10) else h
+    if v in (PIX_NV12, PIX_NV16, PIX_P010, PIX_P210):
+        return [(h, S * w), (ch, S * w)]
+    return [(h, S * w), (ch, S * w // 2), (ch, S * w // 2)]
 
 
 def _chroma_frame(frame, w, h):
@@ -1082,9 +1097,27 @@ class AsyncMultiMapper:
         fix = lambda p: p if p is None or p.strides[1] == p.itemsize else np.ascontiguousarray(p)
         inputs = [(tri,) if isinstance(tri, np.ndarray) else tuple(tri) for tri in inputs]  # a packed UYVY plane
         ip, ipt, planes = _plane_args([tuple(fix(p) for p in tri) for tri in inputs])
-        op, opt, _ = _plane_args([output])
+        op, opt, _ = _plane_args([self._output_planes(output)])
         _check(_lib.octvr_async_push(self._h, ip, ipt, op, opt))
         self._inflight.append((planes, output))
+
+    def _output_planes(self, output):
+        """The output plane set as a tuple; with a converted output format (set_output_format) its planes are
+        checked against plane_shapes: uint8 arrays, or for the 16-bit layouts uint16 arrays or their bytes."""
+        fmt = self.pixel_formats[1]
+        if _PIX_BY_NAME[fmt] in (PIX_YUV420P, PIX_NV12):
+            return output
+        planes = (output,) if isinstance(output, np.ndarray) else tuple(output)
+        want = plane_shapes(fmt, self.out_size[0], self.out_size[1])
+        if len(planes) < len(want):
+            raise ValueError("output: %s takes %d planes, got %d" % (fmt, len(want), len(planes)))
+        for k, (rows, nbytes) in enumerate(want):
+            p = planes[k]
+            if not (isinstance(p, np.ndarray) and p.ndim == 2 and p.dtype in (np.uint8, np.uint16) and
+                    p.strides[1] == p.itemsize and p.shape[0] == rows and p.shape[1] * p.itemsize == nbytes):
+                raise ValueError("output plane %d: expected %d rows of %d bytes (%s) with unit column stride"
+                                 % (k, rows, nbytes, fmt))
+        return planes[:len(want)]
 
     @staticmethod
     def _device_frame(t, w, h, what, fmt="yuv420p"):
@@ -1113,7 +1146,7 @@ class AsyncMultiMapper:
                              % (self.n, len(inputs)))
         fmt = self.pixel_formats[0]
         ins = [self._device_frame(t, w, h, "input %d" % i, fmt) for i, (t, (w, h)) in enumerate(zip(inputs, self.in_sizes))]
-        out = self._device_frame(output, self.out_size[0], self.out_size[1], "output")
+        out = self._device_frame(output, self.out_size[0], self.out_size[1], "output", self.pixel_formats[1])
         ptrs = (_VP * self.n)(*[t.data_ptr() for t in ins])
         pitches = (C.c_size_t * self.n)(*[t.stride(0) for t in ins])
         ev = None
@@ -1142,11 +1175,13 @@ class AsyncMultiMapper:
         (octvr_async_register_output): its frames are then downloaded straight into it.  Planes that are
         views of one array (a contiguous NV12 frame's a[:H] and a[H:]) are locked as one range.  The arrays are
         kept alive until close()."""
+        output = self._output_planes(output)
         op, opt, _ = _plane_args([output])
         _check(_lib.octvr_async_register_output(self._h, op, opt))
         self._registered.append(tuple(output))
 
     def unregister_output(self, output):
+        output = (output,) if isinstance(output, np.ndarray) else output
         op, _, _ = _plane_args([output])
         _check(_lib.octvr_async_unregister_output(self._h, op))
         self._registered = [r for r in self._registered
@@ -1157,11 +1192,24 @@ class AsyncMultiMapper:
         OCTVR_PIX_* values (octvr_async_set_pixel_formats): no frame may be pending, and the output format
         cannot change while output plane sets are registered.  The input format may also be "uyvy422": push then
         takes one packed plane (h rows of 2w bytes) per camera, as a one-tuple or the array itself, and
-        push_device one packed cuda tensor per camera; as the output format it is E_UNSUPPORTED.  "yuyv422",
+        push_device one packed cuda tensor per camera; as the output format it is E_UNSUPPORTED here (set_output_format
+        sets the converted layouts as the output format).  "yuyv422",
         "yuv422p" and "nv16" likewise: input only, planes as push() describes, push_device one cuda tensor of
         frame_shape(fmt, w, h) per camera.  So are the 10-bit "p010", "yuv420p10", "p210" and "yuv422p10": one
         narrowing conversion per frame serves all mappers, which read the pipeline's 8-bit NV12 frames."""
         _check(_lib.octvr_async_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
+
+    def set_output_format(self, out_format):
+        """The layout of the merged frame, any of the ten names or OCTVR_PIX_* values
+        (octvr_async_set_output_format).  "yuv420p" and "nv12" are set_pixel_formats(current input format, it).  A
+        converted layout keeps the input format, puts the mappers on NV12 output and has one kernel per frame merge
+        and convert their region frames: push and register_output then take the layout's planes (plane_shapes: one
+        packed plane, as a one-tuple or the array itself; (Y, UV); or (Y, U, V); uint8 arrays or, for the 16-bit
+        layouts, uint16 arrays or their bytes), push_device an output tensor of frame_shape(fmt, W, H) bytes.  Every
+        region must start at even x and y with its chroma rectangle at their halves (E_INVALID otherwise, as with
+        frames pending or output planes registered in another format).  set_pixel_formats(in, "yuv420p" or "nv12")
+        leaves converted output."""
+        _check(_lib.octvr_async_set_output_format(self._h, _pix_value(out_format)))
 
     @property
     def pixel_formats(self):
