@@ -517,8 +517,10 @@ public:
         int fi = 0, fo = 0;
         pixel_formats(fi, fo);
         // a 4:2:0 image is W x 3H/2, a packed UYVY or YUYV one 2W x H, a YUV422P or NV16 one W x 2H (all CV_8UC1); a
-        // 10-bit one is CV_MAKETYPE(CV_16U, 1) of W columns, or CV_8UC1 of 2W byte columns, with 3H/2 (P010, YUV420P10) or 2H rows
+        // 10-bit one is CV_MAKETYPE(CV_16U, 1) of W columns, or CV_8UC1 of 2W byte columns, with 3H/2 (P010, YUV420P10) or 2H rows;
+        // a v210 one is CV_8UC1 of 128 ceil(W / 48) byte columns and H rows
         auto shaped = [](const cv::cuda::GpuMat& m, const cv::Size& sz, int fmt) {
+            if (fmt == OCTVR_PIX_V210) return m.type() == CV_8UC1 && m.cols == 128 * ((sz.width + 47) / 48) && m.rows == sz.height;
             if (fmt >= OCTVR_PIX_P010 && fmt <= OCTVR_PIX_YUV422P10) {
                 const int rows = fmt >= OCTVR_PIX_P210 ? 2 * sz.height : sz.height / 2 * 3;
                 return m.rows == rows && ((m.type() == CV_MAKETYPE(CV_16U, 1) && m.cols == sz.width) || (m.type() == CV_8UC1 && m.cols == 2 * sz.width));
@@ -535,7 +537,9 @@ public:
             pitch.push_back(inputs[i].step);
         }
         if (output.empty()) {
-            if (fo >= OCTVR_PIX_P010 && fo <= OCTVR_PIX_YUV422P10)
+            if (fo == OCTVR_PIX_V210)
+                output.create(out_.height, 128 * ((out_.width + 47) / 48), CV_8UC1);
+            else if (fo >= OCTVR_PIX_P010 && fo <= OCTVR_PIX_YUV422P10)
                 output.create(fo >= OCTVR_PIX_P210 ? 2 * out_.height : out_.height * 3 / 2, out_.width, CV_MAKETYPE(CV_16U, 1));
             else if (fo == OCTVR_PIX_UYVY422 || fo == OCTVR_PIX_YUYV422)
                 output.create(out_.height, 2 * out_.width, CV_8UC1);

@@ -334,7 +334,28 @@ int octvr_mapper_set_frames_in_flight(octvr_mapper* mapper, int k);
  *       chroma row r to rows 2r and 2r + 1; bytes between a row's 2 W bytes and its pitch are never written.
  * Out-then-in is the identity, and a stitch in any of them is the planar 8-bit stitch of the frames converted by
  * the in rule, stored by the out rule, bit for bit.  octvr_mapper_info reports "yuv10_runs", "yuv10_in_bytes" and
- * "yuv10_out_bytes" for a side in one of these four (the "uyvy_*" and "yuv422_*" keys are then 0). */
+ * "yuv10_out_bytes" for a side in one of these four (the "uyvy_*" and "yuv422_*" keys are then 0).
+ *
+ * OCTVR_PIX_V210: 10-bit 4:2:2 as uncompressed SDI / HDMI capture and playout cards hand it over (DeckLink, AJA,
+ * Bluefish) and as ffmpeg's and QuickTime's `v210` codec stores it; valid for either side independently of the other
+ * side's format, through the same per-slot NV12 frames and footprint conversion.  A W x H frame (W, H even) is H
+ * rows of 16-byte blocks of four little-endian 32-bit words; a word carries three 10-bit components in bits 9..0,
+ * 19..10 and 29..20 (bits 31..30 are ignored on input and written as 0).  Block b of a row holds its pixels
+ * 6 b .. 6 b + 5:
+ *   word 0 = Cb0 | Y0 << 10 | Cr0 << 20      word 1 = Y1 | Cb1 << 10 | Y2 << 20
+ *   word 2 = Cr1 | Y3 << 10 | Cb2 << 20      word 3 = Y4 | Cr2 << 10 | Y5 << 20
+ * with Cb_k, Cr_k the chroma of the pixel pair 6 b + 2 k, 6 b + 2 k + 1.  A row is 128 * ceil(W / 48) bytes (padded
+ * to 48 pixels): on input the components of pixels >= W and the blocks past the last pixel are ignored; on output
+ * every byte of the row is written, those components and blocks as 0; bytes between the row and the pitch are never
+ * written.  `pitch` >= the row's bytes; the base address and the pitch are multiples of 4 (else OCTVR_E_INVALID
+ * before any launch, the output untouched), no other alignment is needed.  The two rules are P210's: in
+ * v8 = min(255, (v10 + 2) >> 2) per component, each chroma row narrowed first, then (c8[2r] + c8[2r + 1] + 1) >> 1;
+ * out v10 = v8 << 2 with chroma row r on rows 2r and 2r + 1.  Out-then-in is the identity, and a v210 stitch is the
+ * planar 8-bit stitch of the frames converted by the in rule, stored by the out rule, bit for bit.
+ * octvr_mapper_info reports "v210_runs", "v210_in_bytes" (the 16-byte blocks the conversion reads per frame: the
+ * blocks that hold a footprint run's pixels, in its two rows, each counted once) and "v210_out_bytes" (the row's
+ * bytes times H at the output size); the "uyvy_*", "yuv422_*" and "yuv10_*" keys are then 0.  Y210, v216 and 12-bit
+ * samples are not taken. */
 enum {
     OCTVR_PIX_YUV420P = 0,
     OCTVR_PIX_NV12 = 1,
@@ -345,7 +366,8 @@ enum {
     OCTVR_PIX_P010 = 32,
     OCTVR_PIX_YUV420P10 = 33,
     OCTVR_PIX_P210 = 34,
-    OCTVR_PIX_YUV422P10 = 35
+    OCTVR_PIX_YUV422P10 = 35,
+    OCTVR_PIX_V210 = 48
 };
 int octvr_mapper_set_pixel_formats(octvr_mapper* mapper, int in_format, int out_format);
 int octvr_mapper_pixel_formats(const octvr_mapper* mapper, int* in_format, int* out_format);
@@ -481,7 +503,13 @@ int octvr_async_info(const octvr_async* async, char* buf, size_t len);
  * addresses: P010 / P210 Y (2 W bytes x H rows) and the U,V plane (2 W bytes x H/2 or H rows), the third entry is
  * ignored; the planar two Y, U and V (U and V W bytes x H/2 or H rows each).  The copy-in packs a footprint run as
  * its two luma rows, then its chroma row(s) in the format's layout: 6 bytes per pixel of the run for 4:2:0, 8 for
- * 4:2:2.  octvr_async_push_device takes one device frame per camera in the Mapper's layout of the format. */
+ * 4:2:2.  octvr_async_push_device takes one device frame per camera in the Mapper's layout of the format.
+ * OCTVR_PIX_V210 is an input format as well: in_planes[3*i] is camera i's one plane (H rows of 128 * ceil(W / 48)
+ * bytes; address and pitch multiples of 4), octvr_async_push_device takes one such device frame per camera.  The
+ * copy-in packs a footprint run as the 16-byte blocks that hold its pixels, those of its first row, then those of its
+ * second.  As the output format, here and in octvr_async_set_output_format, it is OCTVR_E_UNSUPPORTED with nothing
+ * changed: v210 out of the pipeline is not built (merge_pack_kernel's regions would have to start at a multiple of
+ * 6 pixels). */
 int octvr_async_set_pixel_formats(octvr_async* async, int in_format, int out_format);
 int octvr_async_pixel_formats(const octvr_async* async, int* in_format, int* out_format);
 /* The layout of the merged frame, any of the ten OCTVR_PIX_* values (no reference counterpart: a playout card

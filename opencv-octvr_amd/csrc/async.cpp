@@ -281,7 +281,7 @@ struct octvr_async {
         size_t bytes = 0;
     };
     RunPlan native, conv;
-    int conv_bpp = 0;  // packed bytes per pixel of a piece's row conv's offsets were built with (0: no table)
+    int conv_bpp = 0;  // LayoutDesc::run_key conv's offsets were built with: packed bytes per pixel of a piece's row (0: no table)
     bool in_conv() const { return converted_format(in_fmt); }
     const RunPlan& plan() const { return in_conv() ? conv : native; }
     // the unpack launch of a converted input format over its table, from the packed buffer or the caller's frames
@@ -921,6 +921,10 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
             return f == OCTVR_PIX_YUV420P || f == OCTVR_PIX_NV12 || converted_format(f);
         };
         REQUIRE(known(in_format) && known(out_format), "pixel format must be an OCTVR_PIX_* value");
+        if (out_format == OCTVR_PIX_V210)
+            throw OctvrError(OCTVR_E_UNSUPPORTED,
+                             "v210 out of the pipeline is not built: OCTVR_PIX_V210 is an input format here (a Mapper writes "
+                             "it: octvr_mapper_set_pixel_formats)");
         if (converted_format(out_format))
             throw OctvrError(OCTVR_E_UNSUPPORTED,
                              "the converted layouts (4:2:2, 10-bit) are input formats of the pipeline only: its merge, copy-out "
@@ -936,9 +940,9 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
         DeviceGuard dg0(a->device);
         const LayoutDesc in_layout = layout_of(in_format);
         const bool in_conv = in_layout.converted();
-        // the pieces' places in the packed buffer are the format's own: 4, 6 or 8 bytes per pixel of a piece's row;
-        // a switch between them rebuilds the table
-        if (in_conv && a->conv_bpp != in_layout.run_bpp() && !a->native.runs.empty()) {
+        // the pieces' places in the packed buffer are the format's own: 4, 6 or 8 bytes per pixel of a piece's row, or
+        // v210's covering blocks (run_key); a switch between them rebuilds the table
+        if (in_conv && a->conv_bpp != in_layout.run_key() && !a->native.runs.empty()) {
             size_t bytes = 0;
             std::vector<FootRun> t = run_table(in_layout, a->native.runs, a->in_w, bytes);
             REQUIRE(bytes < ((size_t)1 << 32) && t.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
@@ -951,7 +955,7 @@ int octvr_async_set_pixel_formats(octvr_async* a, int in_format, int out_format)
                 }
             a->conv.runs = std::move(t);
             a->conv.bytes = bytes;
-            a->conv_bpp = in_layout.run_bpp();
+            a->conv_bpp = in_layout.run_key();
         }
         // a pipeline with a converted input converts once for all its mappers, which read its NV12 frames
         const int mapper_in = in_conv ? OCTVR_PIX_NV12 : in_format;
@@ -980,6 +984,10 @@ int octvr_async_set_output_format(octvr_async* a, int out_format) {
     return guarded([&] {
         const LayoutDesc d = layout_of(out_format);
         REQUIRE(d.converted(), "pixel format must be an OCTVR_PIX_* value");
+        if (d.v210())
+            throw OctvrError(OCTVR_E_UNSUPPORTED,
+                             "v210 out of the pipeline is not built: merge_pack_kernel places regions by 16-byte chunks of "
+                             "samples, v210's would have to start at a multiple of 6 pixels");
         REQUIRE(a->pending == 0, "frames pending: pop them before changing the output format");
         REQUIRE(out_format == a->out_fmt || a->reg_out.empty(),
                 "output planes are registered: unregister them before changing the output format");

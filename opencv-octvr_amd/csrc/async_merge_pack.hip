@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(256) merge_pack_kernel(uint8_t* __restrict__ o
 
 hipError_t launch_merge_pack(int pix, uint8_t* out, const MergePackTable& t, hipStream_t s) {
     const LayoutDesc d = layout_of(pix);
-    if (!d.converted() || !out || !d.aligned(out, t.pitch)) return hipErrorInvalidValue;  // heads and tails are samples
+    if (!d.converted() || d.v210() || !out || !d.aligned(out, t.pitch)) return hipErrorInvalidValue;  // heads and tails are samples
     if (t.items == 0) return hipSuccess;
     const dim3 grid((t.items + 255u) / 256u);
     with_layout(pix, [&](auto tag) { hipLaunchKernelGGL(merge_pack_kernel<decltype(tag)>, grid, dim3(256), 0, s, out, t); });

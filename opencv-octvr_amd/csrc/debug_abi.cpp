@@ -39,7 +39,7 @@ int octvr_debug_pack_runs(int n_inputs, const int* in_w, const int* in_h, const 
             const int w = in_w[cam], h = in_h[cam];
             REQUIRE(rp < (uint32_t)h / 2 && ng > 0 && g0 < (uint32_t)(w + 7) / 8 && ng <= (uint32_t)(w + 7) / 8 - g0,
                     "run outside its frame");
-            const size_t n = (size_t)d.run_bpp() * (size_t)run_px(w, (int)g0, (int)ng);
+            const size_t n = d.run_bytes(w, (int)g0, (int)ng);
             REQUIRE(off + n <= cap, "buffer too small");
             const size_t got = pack_run(d, packed + off, w, (int)rp, (int)g0, (int)ng, planes + 3 * cam, pitches + 3 * cam);
             REQUIRE(got == n, "pack_run size");

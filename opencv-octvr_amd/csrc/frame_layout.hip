@@ -39,7 +39,18 @@
 //   zero bytes.  With two chroma rows per row pair each NV12 chroma row is read for two destination rows (the
 //   second from L2).  Heads and tails are samples.  Plain loads (the frame was written by the kernel just before)
 //   and plain stores (the caller's next kernel or copy reads the frame).
+// v210_unpack_kernel / v210_pack_kernel (OCTVR_PIX_V210; lane bodies: v210_layout.hpp): the same table, lanes, cache
+//   policy and bounds.  A lane of the unpack takes two 16-byte loads per packed row (the group's two blocks, at any
+//   alignment), narrows each word's three fields where they stand (clamped before they can touch: v10 + 2 carries
+//   out of ten bits), gathers a block's twelve bytes by three permutes, which are UYVY bytes, picks the group's
+//   sixteen by its phase (whole dwords: selects, no divergence), then UYVY's permutes and avg4 and the same three
+//   8-byte stores.  A full group's second block always holds pixels of the group, so no load leaves the row's blocks
+//   that hold pixels; the short last group goes word by word.  A work item of the pack is one 16-byte block of a
+//   destination row: 8 luma and 8 chroma bytes from the same byte offset of their NV12 rows (the last two blocks
+//   with pixels byte by byte), zipped, widened into four words, one 16-byte store, or four dword stores where the
+//   caller's base or pitch puts the block off a 16-byte boundary; the padding blocks are zero stores.
 #include "frame_layout.hpp"
+#include "v210_layout.hpp"
 #include "kernels.hpp"
 #include "octvr_hip.h"
 
@@ -48,6 +59,7 @@ namespace octvr {
 static_assert(OCTVR_PIX_UYVY422 == 16 && OCTVR_PIX_YUYV422 == 17 && OCTVR_PIX_YUV422P == 18 && OCTVR_PIX_NV16 == 19 &&
                   OCTVR_PIX_P010 == 32 && OCTVR_PIX_YUV420P10 == 33 && OCTVR_PIX_P210 == 34 && OCTVR_PIX_YUV422P10 == 35,
               "with_layout's cases are the OCTVR_PIX_* values");
+static_assert(OCTVR_PIX_V210 == 48, "layout_of's v210 case is the OCTVR_PIX_* value");
 
 namespace {
 
@@ -84,6 +96,12 @@ struct PackMem {  // the NV12 frame the kernel before wrote
     __device__ __forceinline__ void store16(uint8_t* p, const Words4& v) const {
         *reinterpret_cast<u32x4*>(p) = u32x4{v.x, v.y, v.z, v.w};
     }
+    // the compiler barrier keeps four neighbouring dword stores four (they would otherwise be merged into one 16-byte
+    // store at a 4-byte aligned address)
+    __device__ __forceinline__ void store4(uint8_t* p, uint32_t v) const {
+        *reinterpret_cast<uint32_t*>(p) = v;
+        asm volatile("" ::: "memory");
+    }
 };
 
 constexpr uint32_t kUnpackLanes = 16;  // lanes of one table piece
@@ -115,12 +133,34 @@ __global__ void __launch_bounds__(256) layout_pack_kernel(const uint8_t* __restr
     pack_lane<L>(PackMem{}, src, out, w, h, pack_item(d, w, h, pitch, reinterpret_cast<uintptr_t>(out), id));
 }
 
+__global__ void __launch_bounds__(256) v210_unpack_kernel(const FootRun* __restrict__ table, int n_pieces, ConvSources src,
+                                                          FootFrames fr) {
+    const int piece = (int)(blockIdx.x * (256u / kUnpackLanes) + threadIdx.x / kUnpackLanes);
+    if (piece >= n_pieces) return;
+    const FootRun r = table[piece];
+    const int cam = (int)(r.cam & 31u);
+    const int w = fr.w[cam], h = fr.h[cam];
+    const uint8_t* const s = src.packed ? src.packed : src.f[cam];
+    const size_t pitch = src.packed ? 0 : src.pitch[cam];
+    uint8_t* const dst = fr.f[cam];
+    for (int k = (int)(threadIdx.x % kUnpackLanes); k < (int)r.ng; k += (int)kUnpackLanes)
+        v210_unpack_lane(UnpackMem{}, s, dst, w, v210_unpack_item(w, h, pitch, r, k));
+}
+
+__global__ void __launch_bounds__(256) v210_pack_kernel(const uint8_t* __restrict__ src, int w, int h, uint8_t* __restrict__ out,
+                                                        size_t pitch, uint32_t items) {
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= items) return;
+    v210_pack_lane(PackMem{}, src, out, v210_pack_item(w, h, pitch, id));
+}
+
 hipError_t launch_layout_unpack(int pix, const FootRun* table, int n_pieces, const ConvSources& src, const FootFrames& frames,
                                 hipStream_t s) {
     if (!converted_format(pix)) return hipErrorInvalidValue;
     if (n_pieces <= 0) return hipSuccess;
     constexpr unsigned per_block = 256u / kUnpackLanes;
     const dim3 grid(((unsigned)n_pieces + per_block - 1u) / per_block);
+    if (pix == OCTVR_PIX_V210) hipLaunchKernelGGL(v210_unpack_kernel, grid, dim3(256), 0, s, table, n_pieces, src, frames);
     with_layout(pix, [&](auto tag) {
         hipLaunchKernelGGL(layout_unpack_kernel<decltype(tag)>, grid, dim3(256), 0, s, table, n_pieces, src, frames);
     });
@@ -132,9 +172,10 @@ hipError_t launch_layout_pack(int pix, const uint8_t* src, int w, int h, uint8_t
     if (!d.converted()) return hipErrorInvalidValue;
     if (w <= 0 || h <= 0 || (w & 1) || (h & 1) || pitch < (size_t)d.row_bytes(w)) return hipErrorInvalidValue;
     if (!d.aligned(out, pitch)) return hipErrorInvalidValue;  // heads and tails are samples
-    const uint64_t items = pack_items(d, w, h);
+    const uint64_t items = d.v210() ? v210_pack_items(w, h) : pack_items(d, w, h);
     if (items >= 0x7FFFFFFFull) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((items + 255u) / 256u));
+    if (d.v210()) hipLaunchKernelGGL(v210_pack_kernel, grid, dim3(256), 0, s, src, w, h, out, pitch, (uint32_t)items);
     with_layout(pix, [&](auto tag) {
         hipLaunchKernelGGL(layout_pack_kernel<decltype(tag)>, grid, dim3(256), 0, s, src, w, h, out, pitch, (uint32_t)items);
     });

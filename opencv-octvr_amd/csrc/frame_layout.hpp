@@ -1,8 +1,10 @@
-// frame_layout.hpp — the arithmetic of the frame layouts (the ten OCTVR_PIX_* values): the planes of a frame and the
-// packing of a footprint run from them (async.cpp copy_in), for every layout; and for the eight capture layouts the
-// Mapper and the pipeline convert to and from their internal 8-bit NV12 frames (the values >= 16) which bytes a work
-// item of layout_unpack_kernel / layout_pack_kernel (frame_layout.hip) loads and which it stores, and the split of
-// footprint runs into the unpack kernel's table.
+// frame_layout.hpp — the arithmetic of the frame layouts (the eleven OCTVR_PIX_* values): the planes of a frame and the
+// packing of a footprint run from them (async.cpp copy_in), for every layout; and for the eight capture layouts of
+// byte and 16-bit samples the Mapper and the pipeline convert to and from their internal 8-bit NV12 frames (the
+// values 16 .. 35) which bytes a work item of layout_unpack_kernel / layout_pack_kernel (frame_layout.hip) loads and
+// which it stores, and the split of footprint runs into the unpack kernel's table.  v210 (48), whose samples are 10
+// bits of a 32-bit word, shares the frame arithmetic, the runs and the table here; its work items and lane bodies
+// are v210_layout.hpp's.
 // No HIP types: the lane bodies are templates over a layout descriptor and a memory policy, so the kernels
 // (non-temporal / vector accesses) and tests/cpp/frame_layout_check.cpp (memcpy against exactly sized heap blocks)
 // execute one definition.
@@ -29,6 +31,8 @@
 //   YUV420P10             2    no   halves     -          1           2 w      3 h / 2        6
 //   P210                  2    yes  pairs      -          2           2 w      2 h            8
 //   YUV422P10             2    no   halves     -          2           2 w      2 h            8
+//   V210                  three 10-bit samples a 32-bit word, six pixels a 16-byte block (v210_layout.hpp):
+//                         128 ceil(w / 48) row bytes, h rows, a run packs its covering blocks (run_bytes)
 // YUV420P and NV12 are native: the kernels read and write them in place, nothing converts them (converted() is
 // false, with_layout has no case for them).  On the host a frame is planes() planes, as octvr_async_push takes
 // them: the packed kind one plane; pairs Y and the U,V plane; halves Y, U and V, each half a row's bytes wide.
@@ -55,9 +59,18 @@
 namespace octvr {
 
 // ---- the layouts ---------------------------------------------------------------------------------------------
-enum ChromaKind : int { kChromaPacked = 0, kChromaPairs = 1, kChromaHalves = 2 };
+enum ChromaKind : int { kChromaPacked = 0, kChromaPairs = 1, kChromaHalves = 2, kChromaV210 = 3 };
+// v210: block b of a row is its pixels [6 b, 6 b + 6) in 16 bytes; a row is padded to 48 pixels.  The blocks that
+// hold the samples of groups [g0, g0 + ng) of a w-wide row (8 pixels a group, cut at the width) are
+// [v210_block0(g0), v210_block0(g0) + v210_blocks(w, g0, ng)).
+constexpr int kV210Block = 16;
+OCTVR_LAYOUT_HD constexpr int v210_row_bytes(int w) { return 128 * ((w + 47) / 48); }
+OCTVR_LAYOUT_HD constexpr int v210_block0(int g0) { return 8 * g0 / 6; }
+OCTVR_LAYOUT_HD constexpr int v210_blocks(int w, int g0, int ng) {
+    return ((8 * (g0 + ng) < w ? 8 * (g0 + ng) : w) + 5) / 6 - v210_block0(g0);
+}
 struct LayoutDesc {
-    int bytes;        // 0: no OCTVR_PIX_* value
+    int bytes;        // 0: no OCTVR_PIX_* value; 4: v210's word of three samples
     bool msb;
     int chroma;
     bool luma_odd;
@@ -66,18 +79,27 @@ struct LayoutDesc {
     OCTVR_LAYOUT_HD constexpr bool converted() const { return bytes != 0 && !native; }
     OCTVR_LAYOUT_HD constexpr bool packed() const { return chroma == kChromaPacked; }
     OCTVR_LAYOUT_HD constexpr bool halves() const { return chroma == kChromaHalves; }
+    OCTVR_LAYOUT_HD constexpr bool v210() const { return chroma == kChromaV210; }
     // bytes per row and rows of a w x h frame
-    OCTVR_LAYOUT_HD constexpr int row_bytes(int w) const { return (packed() ? 2 : 1) * bytes * w; }
-    OCTVR_LAYOUT_HD constexpr int rows(int h) const { return packed() ? h : h + chroma_rows * (h / 2); }
+    OCTVR_LAYOUT_HD constexpr int row_bytes(int w) const { return v210() ? v210_row_bytes(w) : (packed() ? 2 : 1) * bytes * w; }
+    OCTVR_LAYOUT_HD constexpr int rows(int h) const { return packed() || v210() ? h : h + chroma_rows * (h / 2); }
     // the host planes of such a frame, and bytes per row and rows of plane k
-    constexpr int planes() const { return packed() ? 1 : halves() ? 3 : 2; }
+    constexpr int planes() const { return packed() || v210() ? 1 : halves() ? 3 : 2; }
     constexpr int plane_row_bytes(int k, int w) const { return k && halves() ? row_bytes(w) / 2 : row_bytes(w); }
     constexpr int plane_rows(int k, int h) const { return k ? chroma_rows * (h / 2) : h; }
     // packed bytes per pixel of a table piece's row: its two luma rows and its chroma row(s) (pack_run)
-    OCTVR_LAYOUT_HD constexpr int run_bpp() const { return packed() ? 4 : bytes * (2 + chroma_rows); }
-    // a frame of 16-bit words has an even base and an even pitch (a sample's natural alignment)
+    // (v210: 0, a run packs whole blocks)
+    OCTVR_LAYOUT_HD constexpr int run_bpp() const { return v210() ? 0 : packed() ? 4 : bytes * (2 + chroma_rows); }
+    // packed bytes of groups [g0, g0 + ng) of a row pair of a w-wide frame: run_bpp() per pixel of the run's row;
+    // v210: the covering blocks of its two rows.  run_key: what the sizes of a table's pieces depend on.
+    OCTVR_LAYOUT_HD constexpr size_t run_bytes(int w, int g0, int ng) const {
+        return v210() ? (size_t)(2 * kV210Block) * (size_t)v210_blocks(w, g0, ng)
+                      : (size_t)run_bpp() * (size_t)((8 * (g0 + ng) < w ? 8 * (g0 + ng) : w) - 8 * g0);
+    }
+    constexpr int run_key() const { return v210() ? -210 : run_bpp(); }
+    // a frame of 16-bit (32-bit) words has a base and a pitch that are multiples of 2 (4): a word's natural alignment
     bool aligned(const void* base, size_t pitch) const {
-        return bytes != 2 || ((reinterpret_cast<uintptr_t>(base) | pitch) & 1u) == 0;
+        return bytes < 2 || ((reinterpret_cast<uintptr_t>(base) | pitch) & (uintptr_t)(bytes - 1)) == 0;
     }
 };
 // One compile-time descriptor per layout, the tag of the lane bodies' instantiations.
@@ -93,6 +115,8 @@ using LayoutP010 = Layout<2, true, kChromaPairs, false, 1>;
 using LayoutYuv420p10 = Layout<2, false, kChromaHalves, false, 1>;
 using LayoutP210 = Layout<2, true, kChromaPairs, false, 2>;
 using LayoutYuv422p10 = Layout<2, false, kChromaHalves, false, 2>;
+// v210 is no instance of the lane bodies below (with_layout has no case for it): v210_layout.hpp
+constexpr LayoutDesc kLayoutV210{4, false, kChromaV210, false, 2};
 
 // f(tag) of the OCTVR_PIX_* value's layout; false when `pix` is no converted format.
 template <class F>
@@ -109,10 +133,11 @@ inline bool with_layout(int pix, F&& f) {
     }
     return false;
 }
-// The run-time lookup of all ten layouts; bytes == 0 for any other value.
+// The run-time lookup of all eleven layouts; bytes == 0 for any other value.
 inline LayoutDesc layout_of(int pix) {
     if (pix == 0) return LayoutDesc{1, false, kChromaHalves, false, 1, true};  // OCTVR_PIX_YUV420P
     if (pix == 1) return LayoutDesc{1, false, kChromaPairs, false, 1, true};   // OCTVR_PIX_NV12
+    if (pix == 48) return kLayoutV210;                                         // OCTVR_PIX_V210
     LayoutDesc d{0, false, 0, false, 0};
     with_layout(pix, [&](auto tag) { d = decltype(tag)::desc; });
     return d;
@@ -123,7 +148,9 @@ inline bool converted_format(int pix) { return layout_of(pix).converted(); }
 // it address with 32 bits); NULL when it is one.
 inline const char* frame_fault(const LayoutDesc& d, const void* base, size_t pitch, int w, int h, uint64_t limit) {
     if (!base) return "frame is NULL";
-    if (!d.aligned(base, pitch)) return "frame address and pitch must be multiples of 2 for 16-bit samples";
+    if (!d.aligned(base, pitch))
+        return d.v210() ? "frame address and pitch must be multiples of 4 for v210's 32-bit words"
+                        : "frame address and pitch must be multiples of 2 for 16-bit samples";
     if (pitch < (size_t)d.row_bytes(w)) return "pitch smaller than a row of the format";
     if ((uint64_t)pitch * (uint64_t)d.rows(h) >= limit) return "frame larger than 2 GiB";
     return nullptr;
@@ -389,12 +416,18 @@ OCTVR_LAYOUT_HD inline void unpack_lane(const Mem& mem, const uint8_t* src, uint
 }
 
 // Packs run (row pair rp, groups [g0, g0 + ng)) of a w-wide camera at d from host planes laid out as
-// octvr_async_push's: the packed kind planes[0]; pairs planes[0] = Y, planes[1] = U,V pairs; halves
+// octvr_async_push's: the packed kind and v210 planes[0]; pairs planes[0] = Y, planes[1] = U,V pairs; halves
 // planes[0 / 1 / 2] = Y, U, V.  Any of the ten layouts: what the packed-source items above read, and for the native
 // two what unpack_runs_kernel / unpack_runs_nv12_kernel read (w is even, so the U and the V part are half the pair
-// row each and both pack 3 bytes per pixel).  Returns its size, run_bpp() bytes per pixel of the run's row.
+// row each and both pack 3 bytes per pixel).  Returns its size, run_bytes().
 inline size_t pack_run(const LayoutDesc& l, uint8_t* d, int w, int rp, int g0, int ng, const uint8_t* const* planes,
                        const size_t* pitches) {
+    if (l.v210()) {  // the covering blocks of the two rows, rows back to back
+        const size_t nb = (size_t)kV210Block * (size_t)v210_blocks(w, g0, ng);
+        for (int row = 0; row < 2; row++, d += nb)
+            memcpy(d, planes[0] + (size_t)(2 * rp + row) * pitches[0] + (size_t)kV210Block * (size_t)v210_block0(g0), nb);
+        return 2 * nb;
+    }
     const size_t S = (size_t)l.bytes, n = (size_t)run_px(w, g0, ng), G = (size_t)g0;
     const size_t ln = l.packed() ? 2 * n : S * n;  // bytes of the piece in a luma (packed) row
     for (int row = 0; row < 2; row++, d += ln)
@@ -426,7 +459,7 @@ inline std::vector<FootRun> run_table(const LayoutDesc& l, const std::vector<Run
         for (uint32_t k = 0; k < r.ng; k += kWave) {
             const uint32_t ng = r.ng - k < (uint32_t)kWave ? r.ng - k : (uint32_t)kWave;
             t.push_back(FootRun{r.cam, r.g0 + k, ng, (uint32_t)bytes});
-            bytes += (size_t)l.run_bpp() * (size_t)run_px(w, (int)(r.g0 + k), (int)ng);
+            bytes += l.run_bytes(w, (int)(r.g0 + k), (int)ng);
         }
     }
     return t;

@@ -356,6 +356,8 @@ void mapper_set_conv(octvr_mapper* m, int in_fmt, int out_fmt) {
         const std::vector<FootRun> table = run_table(LayoutUyvy::desc, runs, m->in_w, bytes4);
         REQUIRE(bytes4 < ((size_t)1 << 32) && table.size() < 0x7FFFFFFFu, "input footprint exceeds 4 GiB");
         m->conv_in_px = bytes4 / 4;
+        m->conv_in_v210 = 0;
+        for (const FootRun& r : runs) m->conv_in_v210 += kLayoutV210.run_bytes(m->in_w[r.cam & 31u], (int)r.g0, (int)r.ng);
         m->conv_runs = runs.size();
         m->conv_table.upload(table.data(), table.size());
     }

@@ -90,11 +90,12 @@ struct octvr_mapper {
     // on the frame slot's NV12 frames (`pix` carries NV12 for that side).  conv_fmt_in / conv_fmt_out: the side's
     // OCTVR_PIX_* value (0: the side is 8-bit 4:2:0, conv_in / conv_out false); conv_table: the unpack kernel's
     // pieces over this mapper's footprint, the same for every layout (the sources are frames: no piece's `off` is
-    // read); conv_in_px: the pixels of the pieces' rows, run_bpp() packed bytes each.
+    // read); conv_in_px: the pixels of the pieces' rows, run_bpp() packed bytes each; conv_in_v210: the bytes of the
+    // v210 blocks that hold the runs' pixels (LayoutDesc::run_bytes of every run).
     bool conv_in = false, conv_out = false;
     int conv_fmt_in = 0, conv_fmt_out = 0;
     DevBuf<octvr::FootRun> conv_table;
-    size_t conv_runs = 0, conv_in_px = 0;
+    size_t conv_runs = 0, conv_in_px = 0, conv_in_v210 = 0;
     std::vector<octvr::FootRun> conv_foot_runs;  // the runs the table was cut from (octvr_debug_mapper_uyvy_runs)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events, free_events;  // recorded / reusable
     ~octvr_mapper() {

@@ -395,8 +395,8 @@ int octvr_mapper_set_pixel_formats(octvr_mapper* m, int in_format, int out_forma
         };
         REQUIRE(known(in_format) && known(out_format),
                 "pixel format must be OCTVR_PIX_YUV420P, OCTVR_PIX_NV12, OCTVR_PIX_UYVY422, OCTVR_PIX_YUYV422, "
-                "OCTVR_PIX_YUV422P, OCTVR_PIX_NV16, OCTVR_PIX_P010, OCTVR_PIX_YUV420P10, OCTVR_PIX_P210 or "
-                "OCTVR_PIX_YUV422P10");
+                "OCTVR_PIX_YUV422P, OCTVR_PIX_NV16, OCTVR_PIX_P010, OCTVR_PIX_YUV420P10, OCTVR_PIX_P210, "
+                "OCTVR_PIX_YUV422P10 or OCTVR_PIX_V210");
         DeviceGuard dg(m->device);
         mapper_sync(*m);  // stitches in flight keep the layouts they were issued with
         // a side in a converted layout is converted to or from NV12 frames of the frame slot: the stitch sees NV12 there
@@ -521,7 +521,8 @@ int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
         js += ", \"tensor_resized\": " + std::to_string(m->tensor_resized) + ", \"tensor_gathered\": " +
               std::to_string(m->tensor_gathered) + ", \"tensor_no_composite\": " + std::to_string(m->tensor_no_composite);
         // converted sides, per family of layouts (0: the side is not of the family): the footprint runs the unpack
-        // launch converts and the packed bytes it reads per frame (run_bpp(): 4, 6 or 8 per pixel of a piece's row),
+        // launch converts and the packed bytes it reads per frame (run_bpp(): 4, 6 or 8 per pixel of a piece's row; v210:
+        // the blocks that hold a run's pixels),
         // the bytes of the frame the pack launch writes
         const LayoutDesc li = layout_of(m->conv_in ? m->conv_fmt_in : 0), lo = layout_of(m->conv_out ? m->conv_fmt_out : 0);
         const struct {
@@ -529,11 +530,12 @@ int octvr_mapper_info(const octvr_mapper* m, char* buf, size_t len) {
             bool (*is)(int pix, const LayoutDesc& d);
         } families[] = {{"uyvy", [](int pix, const LayoutDesc&) { return pix == OCTVR_PIX_UYVY422; }},
                         {"yuv422", [](int pix, const LayoutDesc& d) { return d.bytes == 1 && pix != OCTVR_PIX_UYVY422; }},
-                        {"yuv10", [](int, const LayoutDesc& d) { return d.bytes == 2; }}};
+                        {"yuv10", [](int, const LayoutDesc& d) { return d.bytes == 2; }},
+                        {"v210", [](int, const LayoutDesc& d) { return d.v210(); }}};
         for (const auto& f : families) {
             const bool i = m->conv_in && f.is(m->conv_fmt_in, li), o = m->conv_out && f.is(m->conv_fmt_out, lo);
             js += std::string(", \"") + f.prefix + "_runs\": " + std::to_string(i ? m->conv_runs : 0) + ", \"" + f.prefix +
-                  "_in_bytes\": " + std::to_string(i ? m->conv_in_px * (size_t)li.run_bpp() : 0) + ", \"" + f.prefix +
+                  "_in_bytes\": " + std::to_string(!i ? 0 : li.v210() ? m->conv_in_v210 : m->conv_in_px * (size_t)li.run_bpp()) + ", \"" + f.prefix +
                   "_out_bytes\": " + std::to_string(o ? (size_t)lo.row_bytes(m->SW) * (size_t)lo.rows(m->SH) : 0);
         }
         if (m->mb) js += ", " + multiband_info(*m->mb);

@@ -535,10 +535,11 @@ class BatchRefs:
 PIX_YUV420P, PIX_NV12, PIX_UYVY422 = 0, 1, 16  # OCTVR_PIX_*
 PIX_YUYV422, PIX_YUV422P, PIX_NV16 = 17, 18, 19  # the other 8-bit 4:2:2 capture layouts
 PIX_P010, PIX_YUV420P10, PIX_P210, PIX_YUV422P10 = 32, 33, 34, 35  # 10-bit samples in 16-bit little-endian words
+PIX_V210 = 48  # 10-bit 4:2:2, three samples a 32-bit word, six pixels a 16-byte block (SDI capture, the v210 codec)
 PIX_NAMES = ("yuv420p", "nv12")  # the 4:2:0 layouts, by value
 _PIX_BY_NAME = {"yuv420p": PIX_YUV420P, "nv12": PIX_NV12, "uyvy422": PIX_UYVY422, "yuyv422": PIX_YUYV422,
                 "yuv422p": PIX_YUV422P, "nv16": PIX_NV16, "p010": PIX_P010, "yuv420p10": PIX_YUV420P10,
-                "p210": PIX_P210, "yuv422p10": PIX_YUV422P10}
+                "p210": PIX_P210, "yuv422p10": PIX_YUV422P10, "v210": PIX_V210}
 _PIX_10BIT = (PIX_P010, PIX_YUV420P10, PIX_P210, PIX_YUV422P10)
 _PIX_BY_VALUE = {v: k for k, v in _PIX_BY_NAME.items()}
 
@@ -547,16 +548,24 @@ def _pix_value(fmt):
     if isinstance(fmt, str):
         if fmt.lower() not in _PIX_BY_NAME:
             raise ValueError("pixel format must be 'yuv420p', 'nv12', 'uyvy422', 'yuyv422', 'yuv422p', 'nv16', "
-                             "'p010', 'yuv420p10', 'p210' or 'yuv422p10'")
+                             "'p010', 'yuv420p10', 'p210', 'yuv422p10' or 'v210'")
         return _PIX_BY_NAME[fmt.lower()]
     return int(fmt)  # the library rejects unknown values (OCTVR_E_INVALID)
+
+
+def v210_row_bytes(w):
+    """Bytes of a w-pixel row of a "v210" frame: 16-byte blocks of six pixels, the row padded to 48 pixels."""
+    return 128 * ((int(w) + 47) // 48)
 
 
 def frame_shape(fmt, w, h):
     """(rows, columns) of a w x h frame in `fmt`: (3h/2, w) for the 4:2:0 layouts, (h, 2w) for "uyvy422" and
     "yuyv422", (2h, w) for "yuv422p" and "nv16".  The 10-bit layouts in bytes (a sample is a 16-bit little-endian
-    word): (3h/2, 2w) for "p010" and "yuv420p10", (2h, 2w) for "p210" and "yuv422p10"."""
+    word): (3h/2, 2w) for "p010" and "yuv420p10", (2h, 2w) for "p210" and "yuv422p10"; (h, v210_row_bytes(w)) for
+    "v210"."""
     v = _pix_value(fmt)
+    if v == PIX_V210:
+        return (int(h), v210_row_bytes(w))
     if v in (PIX_P010, PIX_YUV420P10):
         return (int(h) * 3 // 2, 2 * int(w))
     if v in (PIX_P210, PIX_YUV422P10):
@@ -575,6 +584,8 @@ def plane_shapes(fmt, w, h):
     w, h, S = int(w), int(h), 2 if v in _PIX_10BIT else 1
     if v in (PIX_UYVY422, PIX_YUYV422):
         return [(h, 2 * w)]
+    if v == PIX_V210:
+        return [(h, v210_row_bytes(w))]
     ch = h // 2 if v in (PIX_YUV420P, PIX_NV12, PIX_P010, PIX_YUV420P10) else h
     if v in (PIX_NV12, PIX_NV16, PIX_P010, PIX_P210):
         return [(h, S * w), (ch, S * w)]
@@ -920,14 +931,15 @@ class Mapper:
         halves or U,V pairs; frame_shape gives each layout's shape), the 10-bit "p010", "yuv420p10", "p210" or
         "yuv422p10" (16-bit little-endian words, rows of 2w bytes, base and pitch multiples of 2; narrowed to and
         widened from the mapper's 8-bit frames by v8 = min(255, (v10 + 2) >> 2) and v10 = v8 << 2: the stitch stays
-        the 8-bit one; uint8 tensors of frame_shape, e.g. a uint16 tensor's .view(torch.uint8)), or the OCTVR_PIX_*
-        values (octvr_mapper_set_pixel_formats).  Synchronizes."""
+        the 8-bit one; uint8 tensors of frame_shape, e.g. a uint16 tensor's .view(torch.uint8)), "v210" (10-bit 4:2:2
+        in 32-bit words, h rows of v210_row_bytes(w) bytes, base and pitch multiples of 4; P210's two rules), or the
+        OCTVR_PIX_* values (octvr_mapper_set_pixel_formats).  Synchronizes."""
         _check(_lib.octvr_mapper_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
 
     @property
     def pixel_formats(self):
         """(input layout, output layout) as "yuv420p" / "nv12" / "uyvy422" / "yuyv422" / "yuv422p" / "nv16" / "p010" /
-        "yuv420p10" / "p210" / "yuv422p10"."""
+        "yuv420p10" / "p210" / "yuv422p10" / "v210"."""
         a, b = C.c_int(), C.c_int()
         _check(_lib.octvr_mapper_pixel_formats(self._h, C.byref(a), C.byref(b)))
         return _PIX_BY_VALUE[a.value], _PIX_BY_VALUE[b.value]
@@ -1196,7 +1208,10 @@ class AsyncMultiMapper:
         sets the converted layouts as the output format).  "yuyv422",
         "yuv422p" and "nv16" likewise: input only, planes as push() describes, push_device one cuda tensor of
         frame_shape(fmt, w, h) per camera.  So are the 10-bit "p010", "yuv420p10", "p210" and "yuv422p10": one
-        narrowing conversion per frame serves all mappers, which read the pipeline's 8-bit NV12 frames."""
+        narrowing conversion per frame serves all mappers, which read the pipeline's 8-bit NV12 frames.  "v210" too is
+        an input format (one plane or cuda tensor of h rows of v210_row_bytes(w) bytes per camera, base and pitch
+        multiples of 4); as the output format it is E_UNSUPPORTED here and from set_output_format: v210 out of the
+        pipeline is not built."""
         _check(_lib.octvr_async_set_pixel_formats(self._h, _pix_value(in_format), _pix_value(out_format)))
 
     def set_output_format(self, out_format):
